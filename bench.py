@@ -18,12 +18,15 @@ of detections).
                                            and relays rank 0's JSON line; fails loudly when fewer than N GPUs are visible or when
                                            WORLD_SIZE and --gpus disagree)
 
-The timed region is `--repeats R` (default 5) blocks of EXACTLY K steps, each bracketed by a barrier + synchronize on both sides and
-reduced with MAX over the ranks; `value` / `ms_per_step` are those of the MEDIAN block, `ms_per_step_blocks` lists all of them.
+The timed region is `--repeats R` (default 1) blocks of EXACTLY K = --steps steps, each bracketed by a barrier + synchronize on both sides
+and reduced with MAX over the ranks; `value` / `ms_per_step` are those of the MEDIAN block, `ms_per_step_blocks` lists all of them.
 `rccl_ranks` = the number of distinct ranks an actual all-gather over the process group returned (N > 1: must equal n_gpus),
 `per_rank_fps` = every rank's own frames/s over the median block.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields:
+A plain run sets up, warms up, times the steps and prints the line; `--dump-outputs DIR` also writes what the last timed step returned
+(rank 0's shard) as DIR/<name>.npy.  Everything else it can measure runs only with `--full`.
+
+Prints ONE JSON line (rank 0).  Besides the contract fields, with --full:
   roofline     — for the dominant kernel of the plan: achieved = algorithmic bytes per launch (inputs read once + outputs written
                  once, REAL channel counts; the stored-pitch figure is given beside it) / mean launch duration, the duration measured
                  LIVE with HIP events on the launch stream around that kernel on every timed step.  `traffic` = PMC bytes of that launch
@@ -34,6 +37,8 @@ Prints ONE JSON line (rank 0).  Besides the contract fields:
   mfma         — sum of the dense launches' flops x steps/s against the 2.5 PFLOP/s dense bf16 MFMA peak.
   cpu_baseline — the oracle (OUR CPU port of the reference forward: torch CPU ops, not the reference's own code) timed on this box's
                  host cores at batch 1 and on a bounded multi-frame sample, thread count chosen by a short sweep, CPU model stated.
+  forward_only_fps / plain_forward_detect_fps / compulsory_hbm_frac — the same K steps as forward() alone / as the plain call;
+  collective   — N > 1 / --force-collective: the gather-on against gather-off leg.
 """
 import argparse
 import json
@@ -171,6 +176,29 @@ def cpu_baseline_parallel(ctor, procs, threads, frames):
             'frames_per_process': frames, 'wall_s': round(wall, 3)}
 
 
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: the arrays' data, under the 64 MB cap on everything written
+
+
+def dump_outputs(path, named, seed=0):
+    """--dump-outputs: every array of `named` as <path>/<name>.npy, float32 (integer outputs as float64: exact).  The budget is shared out
+    smallest array first; an array larger than its share is written as <name>_sample.npy, the elements at a fixed set of flat indices
+    drawn from a generator seeded with `seed`, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    items = sorted(named.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        dt = torch.float32 if t.is_floating_point() else torch.float64
+        cap = left // (4 if dt == torch.float32 else 8) // (len(items) - i)
+        t = t.detach()
+        if t.numel() > cap:
+            sel = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t, name = t.reshape(-1)[sel.to(t.device)], name + '_sample'
+        arr = t.to(dt).cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), arr)
+        left -= arr.nbytes
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -286,8 +314,11 @@ def main():
     ap.add_argument('--dense-radar', action='store_true', help='stress variant: U(0,1) in every cell of the radar map instead of 256 occupied cells per frame (SURVEY 8d); nothing is skipped in the first RCBlock')
     ap.add_argument('--opt', action='append', default=[], help='engine option key=value (ach_set_option), repeatable')
     ap.add_argument('--force-collective', action='store_true', help='diagnostic: run the RCCL all-gather of the detection records even at world size 1')
-    ap.add_argument('--ops-json', default=None, help='write the per-launch table (ms, algorithmic bytes) here')
-    ap.add_argument('--repeats', type=int, default=5, help='timed blocks of --steps steps each; value / ms_per_step are the median block')
+    ap.add_argument('--ops-json', default=None, help='write the per-launch table (ms, algorithmic bytes) here (runs the per-launch profile of --full)')
+    ap.add_argument('--repeats', type=int, default=1, help='timed blocks of --steps steps each; value / ms_per_step are the median block')
+    ap.add_argument('--full', action='store_true', help='besides the headline: the per-launch profile and the live roofline probes, the plain and forward-only '
+                                                        'legs, the collective gather-on / gather-off leg and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned (rank 0) as DIR/<name>.npy, at most 64 MB in all')
     ap.add_argument('--cpu-procs', type=int, default=0, help='processes of the frames-parallel CPU-baseline leg (0: host cores / 8, at most 32)')
     ap.add_argument('--no-calibrate', action='store_true', help='with a collective: skip the start-up A/B of the side-stream priority patterns and the gather-on / gather-off overhead leg')
     ap.add_argument('--stub-step-ms', type=float, default=None, help='TEST HOOK: no engine, gloo, a sleep per step (tests/test_bench_launcher.py)')
@@ -346,7 +377,7 @@ def main():
         model.bf16_storage = args.storage
         model.engine_options = dict(base_opts, **extra_opts)
         gathered = [torch.empty(world * B * (args.max_det * 8 + 1), dtype=torch.int32, device=dev) for _ in range(2)] if collective else None
-        state = {'k': 0, 'pending': None, 'inflight': None, 'last': None, 'gather': True}
+        state = {'k': 0, 'pending': None, 'inflight': None, 'last': None, 'result': None, 'gather': True}
         extra = torch.cuda.Stream(dev) if args.extra_stream else None
         scratch = torch.zeros(1024, device=dev) if args.extra_stream else None
 
@@ -361,6 +392,7 @@ def main():
                     state['pending'].wait()
                 state['pending'] = nxt
             state['last'] = (det, se, lane, pc, cnt)
+            state['result'] = res              # what the caller of the timed path receives (--dump-outputs)
 
         def step():
             if extra is not None:
@@ -440,29 +472,31 @@ def main():
         fence()
         out = state['last']
         eng = model.native_engine(tdt, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        # one pass with every launch bracketed by HIP events: find the dominant kernel of the plan
-        outs = (out[0][0], out[0][1], out[0][2], out[1], out[2], out[3])
-        runs = [eng.forward_profiled(x, xr, xp, outs, stream) for _ in range(4)][1:]        # first pass: cold caches
-        prof = [sorted(r[i] for r in runs)[1] for i in range(len(runs[0]))]                  # per launch: the MEDIAN of three profiled passes (a single pass showed 35 us once for a 9 us launch)
-        prof_min = [min(r[i] for r in runs) for i in range(len(runs[0]))]
         full = eng.op_table_full()
-        table = [(o['op'], o['bytes'], o['flops']) for o in full]
-        dom = max(range(len(prof)), key=lambda i: prof[i])
-        eng.set_probe(dom)
-        # the north-star sub-path: neck (SPP .. FPN outputs) + ShuffleAttention + both decoders.  One contiguous run of launches per
-        # stream (all on the caller's stream in the plain plan; the decoders on side stream 2 in the pipelined plan): one range probe each
-        sub_ops = [i for i, o in enumerate(full) if '.fpn.' in o['op'] and '.backbone.' not in o['op']]
+        if args.full or args.ops_json:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            # one pass with every launch bracketed by HIP events: find the dominant kernel of the plan
+            outs = (out[0][0], out[0][1], out[0][2], out[1], out[2], out[3])
+            runs = [eng.forward_profiled(x, xr, xp, outs, stream) for _ in range(4)][1:]        # first pass: cold caches
+            prof = [sorted(r[i] for r in runs)[1] for i in range(len(runs[0]))]                  # per launch: the MEDIAN of three profiled passes (a single pass showed 35 us once for a 9 us launch)
+            prof_min = [min(r[i] for r in runs) for i in range(len(runs[0]))]
         sub_ranges = []
-        for st in sorted({full[i]['stream'] for i in sub_ops}):
-            mine = [i for i in sub_ops if full[i]['stream'] == st]
-            between = [i for i in range(mine[0], mine[-1] + 1) if full[i]['stream'] == st]
-            if between == mine and len(sub_ranges) < 2:                  # contiguous on its stream
-                sub_ranges.append((mine[0], mine[-1]))
-        if len(sub_ranges) != len({full[i]['stream'] for i in sub_ops}):
-            sub_ranges = []
-        for k, (a, b) in enumerate(sub_ranges):
-            eng.set_probe_range(1 + k, a, b)
+        if args.full:
+            table = [(o['op'], o['bytes'], o['flops']) for o in full]
+            dom = max(range(len(prof)), key=lambda i: prof[i])
+            eng.set_probe(dom)
+            # the north-star sub-path: neck (SPP .. FPN outputs) + ShuffleAttention + both decoders.  One contiguous run of launches per
+            # stream (all on the caller's stream in the plain plan; the decoders on side stream 2 in the pipelined plan): one range probe each
+            sub_ops = [i for i, o in enumerate(full) if '.fpn.' in o['op'] and '.backbone.' not in o['op']]
+            for st in sorted({full[i]['stream'] for i in sub_ops}):
+                mine = [i for i in sub_ops if full[i]['stream'] == st]
+                between = [i for i in range(mine[0], mine[-1] + 1) if full[i]['stream'] == st]
+                if between == mine and len(sub_ranges) < 2:                  # contiguous on its stream
+                    sub_ranges.append((mine[0], mine[-1]))
+            if len(sub_ranges) != len({full[i]['stream'] for i in sub_ops}):
+                sub_ranges = []
+            for k, (a, b) in enumerate(sub_ranges):
+                eng.set_probe_range(1 + k, a, b)
 
         blocks, enq = [], []
         for _ in range(max(1, args.repeats)):          # R blocks of exactly K steps, each fenced (barrier + synchronize) on both sides
@@ -475,85 +509,58 @@ def main():
             t1 = time.perf_counter()
             blocks.append(t1 - t0)
             enq.append(th - t0)
-        coll = None
-        if collective and not args.no_calibrate:
-            # what the collective costs THIS run: the same loop with the all-gather switched off (the engine's plan and streams unchanged)
-            on = quick_fps(step, fence)
-            state['gather'] = False
-            off = quick_fps(step, fence)
-            state['gather'] = True
-            coll = dict(calib or {}, rccl_stream_overhead_pct=round((off / on - 1.0) * 100.0, 2), fps_gather_on=round(on, 1), fps_gather_off=round(off, 1),
-                        stream_count={'engine': 1 + len({o['stream'] for o in full} - {0}), 'rccl': 1})
-        probe_ms, probe_n = eng.read_probe()
-        sub_parts = [eng.read_probe_slot(1 + k) for k in range(len(sub_ranges))]
-        sub_ms, sub_n = sum(p[0] for p in sub_parts), min([p[1] for p in sub_parts] or [0])
-        eng.set_probe(-1)
-        for k in range(len(sub_ranges)):
-            eng.set_probe_range(1 + k, -1, -1)
+        if args.dump_outputs and rank == 0:
+            (det, se, lane, pc), (rows, idx, cnt) = state['result']
+            dump_outputs(args.dump_outputs, {'det_p3': det[0], 'det_p4': det[1], 'det_p5': det[2], 'se_seg': se, 'lane_seg': lane, 'pc_seg': pc,
+                                             'nms_rows': rows, 'nms_index': idx, 'nms_count': cnt})
+        coll = calib
         plain = None
-        if pipelined:                      # the same K steps through the plain call (each step joined before the next is enqueued)
-            model.forward_detect(x, xr, xp, args.conf, args.iou, args.max_det)         # the plain plan is a second engine: build it outside the timing
-            pl = []
-            for _ in range(min(3, max(1, args.repeats))):
-                fence()
-                p0 = time.perf_counter()
-                for _ in range(args.steps):
-                    model.forward_detect(x, xr, xp, args.conf, args.iou, args.max_det)
-                fence()
-                pl.append(time.perf_counter() - p0)
-            plain = sorted(pl)[(len(pl) - 1) // 2]
+        if args.full:
+            if collective and not args.no_calibrate:
+                # what the collective costs THIS run: the same loop with the all-gather switched off (the engine's plan and streams unchanged)
+                on = quick_fps(step, fence)
+                state['gather'] = False
+                off = quick_fps(step, fence)
+                state['gather'] = True
+                coll = dict(calib or {}, rccl_stream_overhead_pct=round((off / on - 1.0) * 100.0, 2), fps_gather_on=round(on, 1), fps_gather_off=round(off, 1),
+                            stream_count={'engine': 1 + len({o['stream'] for o in full} - {0}), 'rccl': 1})
+            probe_ms, probe_n = eng.read_probe()
+            sub_parts = [eng.read_probe_slot(1 + k) for k in range(len(sub_ranges))]
+            sub_ms, sub_n = sum(p[0] for p in sub_parts), min([p[1] for p in sub_parts] or [0])
+            eng.set_probe(-1)
+            for k in range(len(sub_ranges)):
+                eng.set_probe_range(1 + k, -1, -1)
+            if pipelined:                      # the same K steps through the plain call (each step joined before the next is enqueued)
+                model.forward_detect(x, xr, xp, args.conf, args.iou, args.max_det)         # the plain plan is a second engine: build it outside the timing
+                pl = []
+                for _ in range(3):
+                    fence()
+                    p0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        model.forward_detect(x, xr, xp, args.conf, args.iou, args.max_det)
+                    fence()
+                    pl.append(time.perf_counter() - p0)
+                plain = sorted(pl)[(len(pl) - 1) // 2]
 
-        # forward-only rate (same inputs, no decode / NMS / gather), for the report
-        fence()
-        f0 = time.perf_counter()
-        for _ in range(args.steps):
-            model(x, xr, xp)
-        fence()
-        f1 = time.perf_counter()
+            # forward-only rate (same inputs, no decode / NMS / gather), for the report
+            fence()
+            f0 = time.perf_counter()
+            for _ in range(args.steps):
+                model(x, xr, xp)
+            fence()
+            f1 = time.perf_counter()
 
-    fwd = torch.tensor([f1 - f0], dtype=torch.float64, device=dev)
-    if collective:
-        dist.all_reduce(fwd, op=dist.ReduceOp.MAX)
-    fwd_elapsed = float(fwd)
+    if args.full:
+        fwd = torch.tensor([f1 - f0], dtype=torch.float64, device=dev)
+        if collective:
+            dist.all_reduce(fwd, op=dist.ReduceOp.MAX)
+        fwd_elapsed = float(fwd)
     head = finish_line(args, rank, world, B, blocks, dev, 'nccl (RCCL)', 'forced' if args.force_collective else None)
-    elapsed = head['ms_per_step'] * 1e-3 * args.steps
     frames = world * B * args.steps
     fps = head['value']
 
     result = None
     if rank == 0:
-        name, dom_bytes, dom_flops = table[dom]
-        esz = 4 if args.dtype == 'f32' else 2
-        achieved = dom_bytes / (probe_ms * 1e-3) / 1e9 if probe_ms > 0 else 0.0
-        roofline = {'bound': 'hbm', 'kernel': name, 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': None,
-                    'algorithmic_bytes_per_launch': dom_bytes, 'layout_bytes_per_launch': full[dom]['layout_bytes'],
-                    'launch_ms': round(probe_ms, 5), 'launches_timed': probe_n, 'launch_ms_isolated': round(prof[dom], 5), 'launch_ms_isolated_best_of_3': round(prof_min[dom], 5),
-                    'frac_isolated': round(dom_bytes / (prof[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if prof[dom] > 0 else None,
-                    'share_of_forward': round(prof[dom] / max(sum(prof), 1e-9), 4)}
-        traffic_file = next((f for f in (os.path.join(ROOT, 'profiles', f'r{r:02d}_traffic_{args.config}.json') for r in (5, 4, 3, 2)) if os.path.exists(f)), '')
-        if traffic_file and args.dtype != 'f32' and B == 64:          # PMC passes are separate rocprofv3 runs (profiles/scripts/profile_config.sh)
-            try:
-                roofline['traffic'] = json.load(open(traffic_file))['ops'].get(name, {}).get('traffic_bytes')
-            except Exception:
-                pass
-        if sub_ranges:
-            # inputs P3/P4/P5 read once + se, lane and the three FPN maps written once (elements per frame)
-            comp_elems = {'S0': 1392000, 'S2': 1504000}.get(kw.get('phi'), None)
-            sub_bytes = sum(full[i]['bytes'] for i in sub_ops)
-            sub_iso = sum(prof[i] for i in sub_ops)
-            comp = comp_elems * esz * B if comp_elems else None
-            fr = lambda by, ms: round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if (by and ms > 0) else None
-            roofline['subpath'] = {
-                'what': f"{full[sub_ops[0]]['op']} .. {full[sub_ops[-1]]['op']}: neck + ShuffleAttention + both seg decoders (in-step = sum of the live range "
-                        f"probes of its {len(sub_ranges)} stream run(s))",
-                'launches': len(sub_ops), 'in_step_ms': round(sub_ms, 5), 'steps_timed': sub_n, 'isolated_ms': round(sub_iso, 5),
-                'compulsory_bytes': comp, 'launch_bytes': sub_bytes,
-                'frac_compulsory_in_step': fr(comp, sub_ms), 'frac_compulsory_isolated': fr(comp, sub_iso),
-                'frac_launch_bytes_in_step': fr(sub_bytes, sub_ms), 'frac_launch_bytes_isolated': fr(sub_bytes, sub_iso)}
-        algo_bytes_frame = (616960 + 1155696) * esz     # inputs + outputs once
-        flops_step = sum(o['flops'] for o in full)
-        mfma_peak = MFMA_PEAK_TFLOPS[args.dtype]
         result = dict(head)
         result['metric'] = ('frames/sec (whole node) EN-GDF-PN-S0 320x320+512pts bs64 @1/2/4/8 GPU' if args.config == 'en_s0'
                             else f'frames/sec (whole node) {args.config} 320x320+512pts bs{B}')
@@ -562,7 +569,7 @@ def main():
                                    f'512 points, batch {B} per GPU, all 5 heads, seeded random weights',
                        'radar_map': 'dense U(0,1) (stress variant)' if args.dense_radar else '256 occupied cells per frame of 102 400 (SURVEY 8d: real maps are > 99 % zeros)',
                        'global_batch': world * B, 'parallelism': f'batch-sharded x{world}' + (' + RCCL all-gather of detections' if world > 1 else ''),
-                       'launches_per_forward': len(table),
+                       'launches_per_forward': len(full),
                        # the storage map VERDICT r3 asked for: what type every class of tensor has in this run
                        'storage': ({'inputs_outputs': 'fp32', 'activations': 'fp32', 'mfma_operands': 'fp32', 'accumulation': 'fp32'} if args.dtype == 'f32' else
                                    {'inputs_outputs': 'bf16' if args.dtype == 'bf16' else 'fp16',
@@ -570,22 +577,58 @@ def main():
                                     'mfma_operands': 'fp16' if (args.dtype == 'f16' or args.storage == 'f16') else 'bf16', 'accumulation': 'fp32',
                                     'note': 'BASELINE configs[1] is bf16 at the boundary; inside, fp16 has the same bytes and MFMA rate with 11 mantissa bits instead of 8 and is what the reference\'s own mixed-precision mode computes in (utils/utils_fit.py:120-121); --storage bf16 = bf16 end to end'})},
             'host_enqueue_ms_per_step': round(sorted(enq)[(len(enq) - 1) // 2] / args.steps * 1e3, 4),
-            'forward_only_fps': round(frames / fwd_elapsed, 2),
             'schedule': 'pipelined submit/wait (batch k+1 enqueued before batch k is joined)' if pipelined else 'plain (every step joined before the next)',
-            'plain_forward_detect_fps': round(B * args.steps / plain, 2) if plain else None,
-            'compulsory_hbm_frac': round(algo_bytes_frame * (frames / fwd_elapsed) / world / 1e9 / HBM_PEAK_GBS, 5),
-            'collective': coll,          # N > 1 / --force-collective: start-up A/B of the side-stream priority patterns, gather-on vs gather-off in this process
-            'roofline': roofline,
-            'mfma': {'flops_per_step': flops_step, 'achieved': round(flops_step * (fps / (world * B)) / 1e12, 2), 'peak': mfma_peak, 'unit': 'TFLOP/s',
-                     'frac': round(flops_step * (fps / (world * B)) / 1e12 / mfma_peak, 5),
-                     'note': '2 x MACs of the dense launches (1x1 / dense convs, linears, attention products) x steps/s per GPU; depthwise convs, the deformable gather and element-wise work are not MFMA work and are excluded'},
+            'full': args.full,
+            'collective': coll,          # N > 1 / --force-collective: start-up A/B of the side-stream priority patterns (+ with --full: gather-on vs gather-off in this process)
         })
+        if args.full:
+            esz = 4 if args.dtype == 'f32' else 2
+            flops_step = sum(o['flops'] for o in full)
+            mfma_peak = MFMA_PEAK_TFLOPS[args.dtype]
+            name, dom_bytes, dom_flops = table[dom]
+            achieved = dom_bytes / (probe_ms * 1e-3) / 1e9 if probe_ms > 0 else 0.0
+            roofline = {'bound': 'hbm', 'kernel': name, 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': None,
+                        'algorithmic_bytes_per_launch': dom_bytes, 'layout_bytes_per_launch': full[dom]['layout_bytes'],
+                        'launch_ms': round(probe_ms, 5), 'launches_timed': probe_n, 'launch_ms_isolated': round(prof[dom], 5), 'launch_ms_isolated_best_of_3': round(prof_min[dom], 5),
+                        'frac_isolated': round(dom_bytes / (prof[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if prof[dom] > 0 else None,
+                        'share_of_forward': round(prof[dom] / max(sum(prof), 1e-9), 4)}
+            traffic_file = next((f for f in (os.path.join(ROOT, 'profiles', f'r{r:02d}_traffic_{args.config}.json') for r in (5, 4, 3, 2)) if os.path.exists(f)), '')
+            if traffic_file and args.dtype != 'f32' and B == 64:          # PMC passes are separate rocprofv3 runs (profiles/scripts/profile_config.sh)
+                try:
+                    roofline['traffic'] = json.load(open(traffic_file))['ops'].get(name, {}).get('traffic_bytes')
+                except Exception:
+                    pass
+            if sub_ranges:
+                # inputs P3/P4/P5 read once + se, lane and the three FPN maps written once (elements per frame)
+                comp_elems = {'S0': 1392000, 'S2': 1504000}.get(kw.get('phi'), None)
+                sub_bytes = sum(full[i]['bytes'] for i in sub_ops)
+                sub_iso = sum(prof[i] for i in sub_ops)
+                comp = comp_elems * esz * B if comp_elems else None
+                fr = lambda by, ms: round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if (by and ms > 0) else None
+                roofline['subpath'] = {
+                    'what': f"{full[sub_ops[0]]['op']} .. {full[sub_ops[-1]]['op']}: neck + ShuffleAttention + both seg decoders (in-step = sum of the live range "
+                            f"probes of its {len(sub_ranges)} stream run(s))",
+                    'launches': len(sub_ops), 'in_step_ms': round(sub_ms, 5), 'steps_timed': sub_n, 'isolated_ms': round(sub_iso, 5),
+                    'compulsory_bytes': comp, 'launch_bytes': sub_bytes,
+                    'frac_compulsory_in_step': fr(comp, sub_ms), 'frac_compulsory_isolated': fr(comp, sub_iso),
+                    'frac_launch_bytes_in_step': fr(sub_bytes, sub_ms), 'frac_launch_bytes_isolated': fr(sub_bytes, sub_iso)}
+            algo_bytes_frame = (616960 + 1155696) * esz     # inputs + outputs once
+            result.update({
+                'forward_only_fps': round(frames / fwd_elapsed, 2),
+                'plain_forward_detect_fps': round(B * args.steps / plain, 2) if plain else None,
+                'compulsory_hbm_frac': round(algo_bytes_frame * (frames / fwd_elapsed) / world / 1e9 / HBM_PEAK_GBS, 5),
+                'roofline': roofline,
+                'mfma': {'flops_per_step': flops_step, 'achieved': round(flops_step * (fps / (world * B)) / 1e12, 2), 'peak': mfma_peak, 'unit': 'TFLOP/s',
+                         'frac': round(flops_step * (fps / (world * B)) / 1e12 / mfma_peak, 5),
+                         'note': '2 x MACs of the dense launches (1x1 / dense convs, linears, attention products) x steps/s per GPU; depthwise convs, the deformable gather and element-wise work are not MFMA work and are excluded'},
+            })
         if args.ops_json:
             rows = [dict(o, ms=round(ms, 5), ms_best_of_3=round(mn, 5)) for o, ms, mn in zip(full, prof, prof_min)]
             os.makedirs(os.path.dirname(os.path.abspath(args.ops_json)), exist_ok=True)
             json.dump({'config': args.config, 'dtype': args.dtype, 'batch': B, 'ops': rows}, open(args.ops_json, 'w'), indent=0)
 
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(model, dict(COMMON, **kw), x, xr, xp, args.cpu_sample, args.cpu_procs)
         else:
             result['cpu_baseline'] = None

@@ -5,7 +5,7 @@ args=$1; shift
 cp achelous_amd/libachelous_hip.so /tmp/lib_keep.so
 for rep in 1 2; do for lib in "$@"; do
   cp $lib achelous_amd/libachelous_hip.so
-  line=$(python bench.py --steps 30 --warmup 5 --no-cpu-baseline $args 2>/dev/null | grep '^{"metric' | tail -1)
+  line=$(python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline $args 2>/dev/null | grep '^{"metric' | tail -1)
   python - "$lib" "$line" <<'PY'
 import json,sys
 d=json.loads(sys.argv[2]); print(f"{sys.argv[1]:50s} {d['value']:9.1f} fps  {d['ms_per_step']:.4f} ms  plain {d.get('plain_forward_detect_fps')}")

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --steps 30 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric' | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%9.1f fps %.4f ms plain %s' % (d['value'], d['ms_per_step'], d.get('plain_forward_detect_fps')))"; }
+run() { python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric' | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%9.1f fps %.4f ms plain %s' % (d['value'], d['ms_per_step'], d.get('plain_forward_detect_fps')))"; }
 cp achelous_amd/libachelous_hip.so /tmp/keep.so
 for rep in 1 2; do
   echo "default          $(run)"

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$root"
 o=gpurun_out/prof_$cfg
 mkdir -p $o
-python bench.py --config $cfg --steps 20 --warmup 5 --ops-json $o/${TAG}_ops_$cfg.json > $o/${TAG}_bench_$cfg.json 2> $o/bench.err
+python bench.py --full --repeats 5 --config $cfg --steps 20 --warmup 5 --ops-json $o/${TAG}_ops_$cfg.json > $o/${TAG}_bench_$cfg.json 2> $o/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline > $o/stats.log 2>&1
 cp $(find $o/stats -name "*kernel_stats.csv" | head -1) $o/${TAG}_kernel_stats_$cfg.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $o/pmc_fetch -- python profiles/scripts/pmc_forward.py --config $cfg --ops-json $o/pmc_ops.json > $o/pmc_fetch.log 2>&1

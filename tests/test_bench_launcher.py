@@ -62,11 +62,66 @@ def test_single_rank_stub_line_has_the_contract_fields():
     assert j['n_gpus'] == 1 and j['rccl_ranks'] == 1 and j['collective_backend'] is None
 
 
+def _dumped(path):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 files (integer outputs as float64), at most 64 MB in all; an array over its share of the budget is written as
+    a sample at seeded flat indices, the same elements on every call."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    named = {'big': torch.randn(5, 4_000_000, generator=g).to(torch.bfloat16), 'mid': torch.randn(3, 1000, generator=g),
+             'count': torch.arange(7, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / 'a'), named)
+    bench.dump_outputs(str(tmp_path / 'b'), named)
+    a, b = _dumped(tmp_path / 'a'), _dumped(tmp_path / 'b')
+    assert sorted(a) == ['big_sample', 'count', 'mid']
+    assert sum(os.path.getsize(tmp_path / 'a' / (k + '.npy')) for k in a) <= 64e6
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a['big_sample'].dtype == np.float32 and a['big_sample'].ndim == 1 and 1e6 < a['big_sample'].size < 20e6
+    assert np.isin(a['big_sample'], named['big'].float().numpy()).all()
+    assert a['mid'].dtype == np.float32 and np.array_equal(a['mid'], named['mid'].numpy())
+    assert a['count'].dtype == np.float64 and np.array_equal(a['count'], np.arange(7))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_what_the_serving_call_returns(tmp_path):
+    """A plain run: exactly --steps timed steps, no --full figures, and --dump-outputs holds the last step's outputs — the same as the
+    plain serving call gives on the bench's seeded weights and inputs."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    from achelous_amd import Achelous
+    from achelous_amd.synth import condition_state_dict, config_seed, make_inputs
+    B = 16
+    r = _run(['--gpus', '1', '--steps', '3', '--warmup', '2', '--batch', str(B), '--dump-outputs', str(tmp_path / 'out')], timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = _one_json_line(r.stdout)
+    assert j['steps'] == 3 and j['repeats'] == 1 and len(j['ms_per_step_blocks']) == 1 and j['ms_per_step'] > 0
+    assert j['full'] is False and 'roofline' not in j and 'forward_only_fps' not in j and j['cpu_baseline'] is None
+    got = _dumped(tmp_path / 'out')
+    assert sum(os.path.getsize(tmp_path / 'out' / (k + '.npy')) for k in got) <= 64e6
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    cid, kw = bench.CONFIGS['en_s0']
+    m = Achelous(**dict(bench.COMMON, **kw)).eval()
+    m.load_state_dict(condition_state_dict(m.state_dict(), seed=0))
+    x, xr, xp = make_inputs(B, config_seed(cid), resolution=320, pc_channels=5)
+    with torch.no_grad():
+        (det, se, lane, pc), (rows, idx, cnt) = m.cuda().forward_detect(*(t.cuda().bfloat16() for t in (x, xr, xp)), 0.35, 0.35, 100)
+    want = {'det_p3': det[0], 'det_p4': det[1], 'det_p5': det[2], 'pc_seg': pc, 'nms_rows': rows, 'nms_index': idx, 'nms_count': cnt}
+    for k, v in want.items():
+        assert np.array_equal(got[k], v.double().cpu().numpy()), k
+
+
 @pytest.mark.gpu
 def test_self_launch_on_every_visible_gpu():
     """N = device_count(): one rank per GPU over RCCL, launched by bench.py itself (N = 1 on the 1-GPU box runs in process)."""
     n = torch.cuda.device_count()
-    r = _run(['--gpus', str(n), '--steps', '4', '--warmup', '2', '--repeats', '2', '--no-cpu-baseline', '--batch', '16'], timeout=900)
+    r = _run(['--gpus', str(n), '--steps', '4', '--warmup', '2', '--repeats', '2', '--full', '--no-cpu-baseline', '--batch', '16'], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _one_json_line(r.stdout)
     assert j['n_gpus'] == n and j['rccl_ranks'] == n and len(j['per_rank_fps']) == n and j['data'] == 'synthetic'
