@@ -14,6 +14,7 @@
 #include "k_train.h"
 #include "k_train2.h"
 #include "k_train3.h"
+#include "k_loss.h"
 
 struct ach_handle {
     ach::EngineBase* eng = nullptr;
@@ -764,6 +765,58 @@ int ach_read_probe(ach_handle* h, float* avg_ms, int* samples) {
     return guarded(h, [&] {
         if (!avg_ms || !samples) throw ach::AchError{ACH_ERR_INVALID, "null pointer"};
         h->eng->read_probe(avg_ms, samples);
+    });
+}
+
+// ---- training losses (k_loss.h): stateless, fp32, no host read — capturable.  Workspaces are the caller's.
+int ach_train_yolo_loss(const float* raw0, const float* raw1, const float* raw2, const float* boxes, const int32_t* counts, int32_t B, int32_t C, int32_t G,
+                        int32_t H0, int32_t W0, int32_t H1, int32_t W1, int32_t H2, int32_t W2, float s0, float s1, float s2, int32_t* claim_anchor, float* claim_cost,
+                        float* claim_iou, int32_t* matched, float* pred_iou, int32_t* num_fg, float* grad, float* partial, float* loss, void* stream) {
+    return train_guard([&] {
+        train_need(raw0 && raw1 && raw2 && boxes && counts && claim_anchor && claim_cost && claim_iou && matched && pred_iou && num_fg && grad && partial && loss, "ach_train_yolo_loss");
+        train_need(B > 0 && B <= 65535 && C > 0 && G > 0 && G <= ach::YL_MAXG && H0 > 0 && W0 > 0 && H1 > 0 && W1 > 0 && H2 > 0 && W2 > 0, "ach_train_yolo_loss");
+        const long n0 = long(H0) * W0, n1 = long(H1) * W1, n2 = long(H2) * W2, A = n0 + n1 + n2;
+        train_need(A <= ach::YL_MAXA, "ach_train_yolo_loss: more anchors than the assignment holds (inputs up to 512 x 512)");
+        ach::YoloLossParams p{};
+        p.raw0 = raw0; p.raw1 = raw1; p.raw2 = raw2;
+        p.W0 = W0; p.W1 = W1; p.W2 = W2; p.off1 = int(n0); p.off2 = int(n0 + n1); p.A = int(A);
+        p.s0 = s0; p.s1 = s1; p.s2 = s2;
+        p.boxes = boxes; p.counts = counts; p.B = B; p.C = C; p.G = G;
+        p.claim_a = claim_anchor; p.claim_cost = claim_cost; p.claim_iou = claim_iou;
+        p.matched = matched; p.pred_iou = pred_iou; p.num_fg = num_fg;
+        p.grad = grad; p.g1 = long(B) * (5 + C) * n0; p.g2 = p.g1 + long(B) * (5 + C) * n1;
+        const unsigned ablocks = unsigned((A + 255) / 256);
+        p.partial = partial; p.loss = loss; p.nblk = int(ablocks) * B;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        ACH_LAUNCH(ach::yolo_assign_kernel, dim3(unsigned(G), unsigned(B)), dim3(256), s, p);
+        ACH_LAUNCH(ach::yolo_resolve_kernel, dim3(unsigned(B)), dim3(256), s, p);
+        ACH_LAUNCH(ach::yolo_loss_kernel, dim3(ablocks, unsigned(B)), dim3(256), s, p);
+        ACH_LAUNCH(ach::yolo_reduce_kernel, dim3(1), dim3(256), s, p);
+    });
+}
+int ach_train_loss_scale(const float* g, const float* scale, float* out, int64_t n, void* stream) {
+    return train_guard([&] {
+        train_need(g && scale && out && n > 0, "ach_train_loss_scale");
+        ach::LossScaleParams p{g, scale, out, long(n)};
+        ACH_LAUNCH(ach::loss_scale_kernel, dim3(unsigned(ach::cdivl(long(n), 256))), dim3(256), static_cast<hipStream_t>(stream), p);
+    });
+}
+// workgroups of the segmentation-loss kernels: 256 threads x V pixels each, grid-stride above 768 = three resident workgroups on each of the 256 compute units
+// (measured at batch 32, 9 classes: 0.180 ms forward + backward against 0.192 with 1024 and 0.204 with 512; the caller's `partial` holds 1024 rows)
+static int seg_loss_blocks(long items) { return int(std::max<long>(1, std::min<long>(ach::cdivl(items, 256), 768))); }
+int ach_train_seg_loss(const float* logits, const void* labels, int32_t label_kind, const float* weights, int32_t B, int32_t C, int64_t HW, int32_t mode, int32_t dice,
+                       float alpha, float gamma, float beta, float smooth, float* partial, float* stats, const float* cot, float* dlogits, void* stream) {
+    return train_guard([&] {                                 /* forward when cot == NULL (-> stats), backward otherwise (stats, cot -> dlogits) */
+        train_need(logits && labels && partial && stats && B > 0 && C > 0 && C <= ach::SEG_MAXC && HW > 0 && label_kind >= 0 && label_kind <= 2 && mode >= 0 && mode <= 2,
+                   "ach_train_seg_loss");
+        train_need(mode == 2 || weights != nullptr, "ach_train_seg_loss: class weights");
+        train_need(cot ? dlogits != nullptr : true, "ach_train_seg_loss");
+        ach::SegLossParams p{logits, labels, label_kind, weights, B, C, long(HW), mode, dice, alpha, gamma, beta, smooth, partial, 0, stats, cot, dlogits};
+        const bool quad = (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15u) == 0;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        p.nblk = seg_loss_blocks(long(B) * (quad ? HW / 4 : HW));
+        if (quad) ach::seg_loss_launch<4>(p, cot != nullptr, s); else ach::seg_loss_launch<1>(p, cot != nullptr, s);
+        if (!cot) ACH_LAUNCH(ach::seg_reduce_kernel, dim3(1), dim3(256), s, p);
     });
 }
 

@@ -357,6 +357,25 @@ int ach_train_pn2_group_bwd(const int32_t* group_idx, const float* dgrouped, flo
 int ach_train_pn2_interp(const float* xyz1, const float* xyz2, const float* skip, int32_t C1, const float* sparse, int32_t C2, float* out, float* dskip, float* dsparse_zeroed,
                          const float* dout, int32_t B, int32_t n, int32_t s, void* stream);
 
+/* Training losses (achelous_amd/csrc/k_loss.h; achelous_amd/losses.py): forward and gradient of the reference's losses without a host read, so that a training
+ * step with its loss can be captured into a graph.  fp32, contiguous; every workspace belongs to the caller; the same inputs give the same bits.
+ *   ach_train_yolo_loss   YOLOX loss with SimOTA assignment (loss/detection_loss.py:60-411) on the three RAW head maps raw_k [B, 5 + C, H_k, W_k] (not modified) and
+ *                         packed labels boxes [B, G, 5] = (cx, cy, w, h in input pixels, class), counts [B] (G <= 128; H0*W0 + H1*W1 + H2*W2 <= 5376).
+ *                         Four launches: assign (claims [B, G, 10]: anchor or -1, cost, IoU), resolve (matched [B, A] box or -1, pred_iou [B, A], num_fg [B]),
+ *                         loss-and-gradient (grad: d loss / d raw_0 | raw_1 | raw_2, flat, each laid out as its map; partial [B * ceil(A / 256)]), reducer (loss [1]).
+ *                         Equal costs go to the lowest anchor index, then the lowest box index.
+ *   ach_train_loss_scale  out[i] = g[i] * scale[0], the scale read on the device (a stored gradient times the incoming cotangent)
+ *   ach_train_seg_loss    loss/segmentation_loss.py:9-59 on logits [B, C, HW] (C <= 16) and INTEGER labels [B, HW] (label_kind 0 int64, 1 int32, 2 uint8; C and anything
+ *                         outside 0..C-1 = ignored): mode 0 weighted CE, 1 focal, 2 none; dice != 0 adds the Dice loss with the one-hot target taken from the label.
+ *                         cot == NULL: forward, two launches -> stats[0] = loss, stats[1 .. 2 + 2 C) = what the backward needs; partial holds 1024 * (2 + 3 C) floats.
+ *                         cot != NULL: backward, one launch: dlogits = cot[0] * d loss / d logits from logits, labels and the forward's stats. */
+int ach_train_yolo_loss(const float* raw0, const float* raw1, const float* raw2, const float* boxes, const int32_t* counts, int32_t B, int32_t C, int32_t G,
+                        int32_t H0, int32_t W0, int32_t H1, int32_t W1, int32_t H2, int32_t W2, float s0, float s1, float s2, int32_t* claim_anchor, float* claim_cost,
+                        float* claim_iou, int32_t* matched, float* pred_iou, int32_t* num_fg, float* grad, float* partial, float* loss, void* stream);
+int ach_train_loss_scale(const float* g, const float* scale, float* out, int64_t n, void* stream);
+int ach_train_seg_loss(const float* logits, const void* labels, int32_t label_kind, const float* weights, int32_t B, int32_t C, int64_t HW, int32_t mode, int32_t dice,
+                       float alpha, float gamma, float beta, float smooth, float* partial, float* stats, const float* cot, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
