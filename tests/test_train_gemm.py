@@ -30,6 +30,10 @@ CASES = [
     (100, 20, 50, 1, 0, 2, 0, 0, True, 0),           # 64 x 32 block tile, B contiguous along its 20 columns (the 32-row single-element staging)
     (100, 24, 50, 0, 1, 2, 0, 0, False, 1),          # 64 x 32, unaligned
     (20, 100, 50, 1, 0, 2, 0, 1, True, 0),           # 32 x 64, A stored K x M
+    # weight gradients of a 320 x 320 training step (K = H * W per sample, batch 8): the split-K count at its cap of 2048 with one output tile, and two tiles at 1024 each
+    (1, 32, 102400, 0, 1, 8, 1, 0, False, 0),
+    (3, 27, 102400, 0, 1, 8, 1, 0, False, 0),
+    (8, 72, 25600, 0, 1, 8, 1, 0, False, 0),
 ]
 
 

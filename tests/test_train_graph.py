@@ -129,17 +129,22 @@ def _oracle_training_reference(sd, kw, x, xr, xp, cot, dtype=torch.float64):
     return [t.detach().double() for t in outs], {n: v.grad.double() for n, v in o.sd.items() if v.is_floating_point() and v.requires_grad and v.grad is not None}
 
 
-ORACLE_CASES = [('S2', True, 64, 'en_s2'), ('S0', False, 64, 'en_s0'), ('S2', True, 64, 'mv_s2'), ('S0', True, 64, 'en_s0_cdf')]
+ORACLE_CASES = [('S2', True, 64, 'en_s2'), ('S0', False, 64, 'en_s0'), ('S2', True, 64, 'mv_s2'), ('S0', True, 64, 'en_s0_cdf'), ('S0', True, 320, 'en_s0')]
+# The 320 px case is one whole step at the size training runs at, where api.cpp dispatches the sliced reductions, split-K and the four-per-thread kernels.  Batch 4, not 2:
+# PointNet's STN normalises its fc layers over the batch, and at 2 samples torch's own float32 is 50 % off the float64 truth.  At this size the step is well enough
+# conditioned to be held to the yardstick alone (`strict`): outputs and gradients within 6 x torch-float32's own error, no 6e-2 floor.  Measured under the emulation:
+# outputs 6e-6 to 2e-5 (torch float32: 7e-6 to 1e-3), median gradient error 4e-3 (1.5e-2), worst ratio to the yardstick over the 527 gradients 2.6.
+ORACLE_SETTINGS = {320: dict(batch=4, points=512, radar_cells=256, strict=True)}
 
 
-def _check_against_oracle_autograd(dev, phi, spp, res, fixture):
+def _check_against_oracle_autograd(dev, phi, spp, res, fixture, batch=2, points=32, radar_cells=12, strict=False):
     from golden_util import Golden, ctor_kwargs
     kw = dict(ctor_kwargs(Golden(fixture).meta), resolution=res, spp=spp)
     m = Achelous(**kw)
     sd = condition_state_dict(m.state_dict(), seed=0)
     m.load_state_dict(sd, strict=True)
     m = m.to(dev).train()
-    x, xr, xp = make_inputs(2, 13, resolution=res, num_points=32, pc_channels=kw['pc_channels'], radar_cells=12)
+    x, xr, xp = make_inputs(batch, 13, resolution=res, num_points=points, pc_channels=kw['pc_channels'], radar_cells=radar_cells)
     det, se, lane, pc = m(x.to(dev), xr.to(dev), xp.to(dev))
     outs = [*det, se, lane, pc]
     g = torch.Generator().manual_seed(3)
@@ -147,11 +152,14 @@ def _check_against_oracle_autograd(dev, phi, spp, res, fixture):
     sum((a * c.to(dev)).sum() for a, c in zip(outs, cot)).backward()
     okw = {k: kw[k] for k in ('num_det', 'num_seg', 'phi', 'backbone', 'neck', 'pc_seg', 'pc_channels', 'pc_classes', 'nano_head', 'spp', 'resolution')}
     ref_outs, ref_grads = _oracle_training_reference(sd, okw, x, xr, xp, cot)
-    _, f32_grads = _oracle_training_reference(sd, okw, x, xr, xp, cot, torch.float32)        # torch's own float32 evaluation: the yardstick
-    for a, b in zip(outs, ref_outs):
-        assert ((a.detach().cpu().double() - b).norm() / b.norm()).item() < 5e-3
+    f32_outs, f32_grads = _oracle_training_reference(sd, okw, x, xr, xp, cot, torch.float32)        # torch's own float32 evaluation: the yardstick
+    for k, (a, b, c) in enumerate(zip(outs, ref_outs, f32_outs)):
+        err, yard = ((a.detach().cpu().double() - b).norm() / b.norm()).item(), ((c - b).norm() / b.norm()).item()
+        assert err < 5e-3, (f'output {k}', err)
+        if strict:
+            assert err <= 6 * yard, (f'output {k}', err, yard)
     gscale = max(float(v.abs().max()) for v in ref_grads.values())
-    checked = 0
+    checked, worst = 0, (0.0, None)
     for k, p in m.named_parameters():
         if k not in ref_grads:
             assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
@@ -159,11 +167,19 @@ def _check_against_oracle_autograd(dev, phi, spp, res, fixture):
         ref, got = ref_grads[k], p.grad.detach().cpu().double()
         err = float((got - ref).norm() / (ref.norm() + 1e-300))
         yard = float((f32_grads[k] - ref).norm() / (ref.norm() + 1e-300))
-        # a wiring check (a wrong graph is off by O(1)): BatchNorm over 2 frames of 2x2 maps and PointNet's max over 32 points make a
-        # float32 step deviate from the float64 truth by several per cent on some tensors — torch's own float32 does the same
-        assert err < max(6e-2, 6 * yard) or float((got - ref).abs().max()) <= ZERO_GRAD_FLOOR * gscale, (k, err, yard)
+        at_floor = float((got - ref).abs().max()) <= ZERO_GRAD_FLOOR * gscale
+        if strict:
+            assert err <= 6 * yard or at_floor, (k, err, yard)
+            if not at_floor and err / (yard + 1e-300) > worst[0]:
+                worst = (err / (yard + 1e-300), k)
+        else:
+            # a wiring check (a wrong graph is off by O(1)): BatchNorm over 2 frames of 2x2 maps and PointNet's max over 32 points make a
+            # float32 step deviate from the float64 truth by several per cent on some tensors — torch's own float32 does the same
+            assert err < max(6e-2, 6 * yard) or at_floor, (k, err, yard)
         checked += 1
     assert checked > 500
+    if strict:
+        print(f'{checked} gradients; the worst ratio to the yardstick: {worst[0]:.2f} ({worst[1]})')
 
 
 @pytest.mark.parametrize('phi,spp,res,fixture', ORACLE_CASES)
@@ -174,7 +190,7 @@ def test_emulated_training_graph_matches_autograd_on_the_oracle(phi, spp, res, f
     from emu_util import emu_library
     train_ops._lib.test_library = emu_library()
     try:
-        _check_against_oracle_autograd('cpu', phi, spp, res, fixture)
+        _check_against_oracle_autograd('cpu', phi, spp, res, fixture, **ORACLE_SETTINGS.get(res, {}))
     finally:
         train_ops._lib.test_library = None
 
@@ -182,7 +198,7 @@ def test_emulated_training_graph_matches_autograd_on_the_oracle(phi, spp, res, f
 @pytest.mark.gpu
 @pytest.mark.parametrize('phi,spp,res,fixture', ORACLE_CASES)
 def test_gpu_training_graph_matches_autograd_on_the_oracle(phi, spp, res, fixture):
-    _check_against_oracle_autograd('cuda', phi, spp, res, fixture)
+    _check_against_oracle_autograd('cuda', phi, spp, res, fixture, **ORACLE_SETTINGS.get(res, {}))
 
 
 @pytest.mark.gpu

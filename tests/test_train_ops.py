@@ -16,7 +16,7 @@ def _reference(cin, cout, relu, seed):
     return conv, bn
 
 
-def _run(dev, B, cin, cout, N, relu, seed=0):
+def _run(dev, B, cin, cout, N, relu, seed=0, conv_bias=None):
     """Truth = the torch layers in float64, with ONE concession that makes the comparison well-posed: where a BatchNorm output lies within rounding of zero, on which side of it a
     float32 evaluation lands — and with that one whole term of dbeta / dgamma / dW / dx — depends on the summation order of the convolution (33 M outputs in the largest GPU case:
     a handful of such elements, in torch's own float32 kernels as much as in ours).  The truth's backward therefore uses the native layer's ReLU mask, after checking that the two
@@ -26,11 +26,15 @@ def _run(dev, B, cin, cout, N, relu, seed=0):
     x = torch.randn(B, cin, N, generator=g)
     dy = torch.randn(B, cout, N, generator=g)
     layer.conv.load_state_dict(_reference(cin, cout, relu, seed)[0].state_dict()); layer.bn.load_state_dict(_reference(cin, cout, relu, seed)[1].state_dict())
+    if conv_bias is not None:
+        torch.nn.init.constant_(layer.conv.bias, conv_bias)
     layer = layer.to(dev).train()
     xn = x.clone().to(dev).requires_grad_(True)
     yn = layer(xn)
     yn.backward(dy.to(dev))
     conv, bn = _reference(cin, cout, relu, seed)
+    if conv_bias is not None:
+        torch.nn.init.constant_(conv.bias, conv_bias)
     conv, bn = conv.double().train(), bn.double().train()
     xr = x.clone().double().requires_grad_(True)
     pre = bn(conv(xr))
@@ -65,6 +69,23 @@ def test_emulated_shared_mlp_forward_backward_match_autograd(B, cin, cout, N, re
         _run('cpu', B, cin, cout, N, relu)
     finally:
         train_ops._lib.test_library = None
+
+
+def test_emulated_shared_mlp_with_mean_dominated_pre_activations():
+    """A convolution bias of 1000 in front of the BatchNorm: the statistics are taken over values whose mean is a thousand times their spread (a one-pass
+    variance E[z^2] - E[z]^2 has no correct digit left in float32 there).  Without the ReLU: a float32 value near 1000 has an ulp of 6e-5, above the 2e-5 within which
+    `_run` lets the two ReLU masks differ — with it the case would measure on which side of zero a rounding falls, not the statistics."""
+    from emu_util import emu_library
+    train_ops._lib.test_library = emu_library()
+    try:
+        print(_run('cpu', 3, 64, 128, 100, False, conv_bias=1000.0))
+    finally:
+        train_ops._lib.test_library = None
+
+
+@pytest.mark.gpu
+def test_gpu_shared_mlp_with_mean_dominated_pre_activations():
+    print(_run('cuda', 64, 5, 64, 512, False, conv_bias=1000.0))
 
 
 @pytest.mark.gpu
