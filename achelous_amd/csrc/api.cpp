@@ -15,6 +15,7 @@
 #include "k_train2.h"
 #include "k_train3.h"
 #include "k_loss.h"
+#include "k_metrics.h"
 
 struct ach_handle {
     ach::EngineBase* eng = nullptr;
@@ -817,6 +818,44 @@ int ach_train_seg_loss(const float* logits, const void* labels, int32_t label_ki
         p.nblk = seg_loss_blocks(long(B) * (quad ? HW / 4 : HW));
         if (quad) ach::seg_loss_launch<4>(p, cot != nullptr, s); else ach::seg_loss_launch<1>(p, cot != nullptr, s);
         if (!cot) ACH_LAUNCH(ach::seg_reduce_kernel, dim3(1), dim3(256), s, p);
+    });
+}
+
+// ---- validation metrics (k_metrics.h): stateless, no host read, no synchronisation — one launch each.  Every buffer is the caller's.
+int ach_eval_confusion(const void* pred, int32_t pred_kind, int32_t layout, const void* labels, int32_t label_kind, int32_t B, int32_t n, int64_t HW, uint64_t* hist,
+                       void* stream) {
+    return train_guard([&] {
+        train_need(pred && labels && hist && B > 0 && HW > 0 && pred_kind >= 0 && pred_kind <= 3 && (layout == 0 || layout == 1) && label_kind >= 0 && label_kind <= 2,
+                   "ach_eval_confusion");
+        train_need(n >= 1 && n <= ach::CONF_MAXN, "ach_eval_confusion: 1 <= n <= 16 classes");
+        ach::ConfusionParams p{pred, layout, labels, label_kind, B, n, long(HW), reinterpret_cast<unsigned long long*>(hist)};
+        const int V = ach::conf_vec(pred_kind);
+        const bool vec = (pred_kind == ach::CONF_MAP_U8 || layout == 0) && HW % V == 0 &&
+                         ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(labels)) & 15u) == 0;
+        const long items = long(B) * (vec ? HW / V : HW);
+        const int nblk = int(std::max<long>(1, std::min<long>(ach::cdivl(items, 256), ach::CONF_BLOCKS)));
+        train_need(ach::cdivl(long(B) * HW, nblk) < (1L << 31), "ach_eval_confusion: too many pixels for one call (the per-workgroup bins are 32-bit)");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (pred_kind == ach::CONF_F32) ach::confusion_launch<float>(p, vec, nblk, s);
+        else if (pred_kind == ach::CONF_BF16) ach::confusion_launch<ach::bf16_t>(p, vec, nblk, s);
+        else if (pred_kind == ach::CONF_F16) ach::confusion_launch<ach::f16_t>(p, vec, nblk, s);
+        else ach::confusion_launch<ach::conf_u8>(p, vec, nblk, s);
+    });
+}
+int ach_eval_match(const float* rows, const int32_t* counts, int32_t yx_order, int32_t truncate, const float* gt, const uint8_t* difficult, const int32_t* gt_counts,
+                   int32_t B, int32_t max_det, int32_t G, int32_t C, const double* thresholds, int32_t T, uint8_t* flags, int32_t* match, double* iou, float* score,
+                   uint64_t* gt_per_class, void* stream) {
+    return train_guard([&] {
+        train_need(rows && counts && gt && gt_counts && thresholds && flags && match && iou && score && gt_per_class, "ach_eval_match");
+        train_need(B > 0 && max_det > 0 && max_det <= ach::MATCH_MAXD && G > 0 && G <= ach::MATCH_MAXG && C > 0 && T > 0 && T <= ach::MATCH_MAXT,
+                   "ach_eval_match: max_det <= 1024, G <= 128, T <= 10");
+        ach::MatchParams p{};
+        p.rows = rows; p.counts = counts; p.yx_order = yx_order != 0; p.truncate = truncate != 0;
+        p.gt = gt; p.difficult = difficult; p.gt_counts = gt_counts;
+        p.B = B; p.D = max_det; p.G = G; p.C = C; p.T = T;
+        for (int t = 0; t < T; ++t) p.thr[t] = thresholds[t];
+        p.flags = flags; p.match = match; p.iou = iou; p.score = score; p.gt_per_class = reinterpret_cast<unsigned long long*>(gt_per_class);
+        ACH_LAUNCH(ach::match_kernel, dim3(unsigned(B)), dim3(256), static_cast<hipStream_t>(stream), p);
     });
 }
 

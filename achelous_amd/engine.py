@@ -40,7 +40,8 @@ class NativeLibrary:
                'ach_normalize_points', 'ach_preprocess_image', 'ach_seg_argmax', 'ach_seg_resize_argmax', 'ach_correct_boxes', 'ach_train_pn2_fps', 'ach_train_pn2_group', 'ach_train_pn2_group_bwd', 'ach_train_pn2_interp', 'ach_train_gemm', 'ach_train_gemm_p', 'ach_train_set_gemm_precision', 'ach_train_get_gemm_precision', 'ach_train_bn_stats', 'ach_train_bn_running', 'ach_train_bn_relu_fwd', 'ach_train_bn_relu_bwd', 'ach_train_dw3x3', 'ach_train_dw3x3_wgrad', 'ach_train_max_points', 'ach_train_log_softmax', 'ach_resample_pass_u8', 'ach_train_act', 'ach_train_mul', 'ach_train_layernorm', 'ach_train_layernorm_bwd', 'ach_train_dwconv', 'ach_train_dwconv_wgrad',
                'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
                'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
-               'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss')
+               'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss',
+               'ach_eval_confusion', 'ach_eval_match')
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -142,7 +143,9 @@ class NativeLibrary:
                            ('ach_train_deform_bwd', [vp] * 7 + [i32] * 8 + [vp]),
                            ('ach_train_yolo_loss', [vp] * 5 + [i32] * 9 + [f32] * 3 + [vp] * 10),
                            ('ach_train_loss_scale', [vp, vp, vp, i64, vp]),
-                           ('ach_train_seg_loss', [vp, vp, i32, vp, i32, i32, i64, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp])):
+                           ('ach_train_seg_loss', [vp, vp, i32, vp, i32, i32, i64, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
+                           ('ach_eval_confusion', [vp, i32, i32, vp, i32, i32, i32, i64, vp, vp]),
+                           ('ach_eval_match', [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp])):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = ctypes.c_int
         L.ach_record_words.argtypes = [i32, i32]

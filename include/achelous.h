@@ -376,6 +376,27 @@ int ach_train_loss_scale(const float* g, const float* scale, float* out, int64_t
 int ach_train_seg_loss(const float* logits, const void* labels, int32_t label_kind, const float* weights, int32_t B, int32_t C, int64_t HW, int32_t mode, int32_t dice,
                        float alpha, float gamma, float beta, float smooth, float* partial, float* stats, const float* cot, float* dlogits, void* stream);
 
+/* Validation metrics (achelous_amd/csrc/k_metrics.h; achelous_amd/metrics.py): the per-batch half of the reference's per-epoch evaluation, one launch each, with
+ * no host read and no synchronisation inside.  Every buffer belongs to the caller; both ADD to their accumulators and never clear them.
+ *   ach_eval_confusion  utils_seg/utils_metrics.py:31-33 `fast_hist` (and the counts of utils_seg_pc/utils_metrics.py `mean_iou`) with the arg-max fused in:
+ *                       hist[n * label + pred] += 1 into a uint64 [n, n] (n <= 16).  pred_kind 0 / 1 / 2: fp32 / bf16 / fp16 logits, layout 0 [B, n, HW] or
+ *                       1 [B, HW, n], equal values go to the LOWEST class (numpy / torch.argmax; NaN logits: unspecified); pred_kind 3: a uint8 class map
+ *                       [B, HW] (what ach_seg_resize_argmax writes; layout ignored; a value >= n is dropped).  labels [B, HW], label_kind as
+ *                       ach_train_seg_loss (0 int64, 1 int32, 2 uint8); a pixel counts only if 0 <= label < n.  Integer adds: the same bits on every run.
+ *   ach_eval_match      utils/utils_map.py:462-498 in parallel form, one workgroup per image.  rows [B, max_det, 7] with counts [B]: columns
+ *                       (x1, y1, x2, y2, obj, cls_conf, class) as ach_nms writes them, or (y1, x1, y2, x2, ...) as ach_correct_boxes does (yx_order = 1);
+ *                       truncate = 1 applies the int() of utils/callbacks.py:216-217 to the four coordinates.  gt [B, G, 5] = (x1, y1, x2, y2, class),
+ *                       G <= 128, difficult [B, G] or NULL, gt_counts [B]; max_det <= 1024; thresholds: T <= 10 doubles in HOST memory, read before the launch.
+ *                       Per detection: score = obj * cls_conf (fp32), the best same-class box of its image by float64 IoU with the +1 pixel convention
+ *                       (the first box reaching the maximum wins) -> match [B, max_det] (-1: none), iou [B, max_det] (-1: no overlap), score [B, max_det],
+ *                       and per threshold flags [T, B, max_det]: 0 empty slot, 1 tp, 2 fp, 3 ignored (matched a difficult box).  Rank inside an image is
+ *                       score descending, then slot ascending.  gt_per_class [C] uint64 += the non-difficult boxes of each class. */
+int ach_eval_confusion(const void* pred, int32_t pred_kind, int32_t layout, const void* labels, int32_t label_kind, int32_t B, int32_t n, int64_t HW, uint64_t* hist,
+                       void* stream);
+int ach_eval_match(const float* rows, const int32_t* counts, int32_t yx_order, int32_t truncate, const float* gt, const uint8_t* difficult, const int32_t* gt_counts,
+                   int32_t B, int32_t max_det, int32_t G, int32_t C, const double* thresholds, int32_t T, uint8_t* flags, int32_t* match, double* iou, float* score,
+                   uint64_t* gt_per_class, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
