@@ -80,7 +80,7 @@ __device__ __forceinline__ void pn2_fps_level(const FpsParams& p) {
             const unsigned long long mask = wave_ballot64(dist[k] == smax);
             if (nxt < 0 && mask) nxt = 64 * k + __ffsll((long long)mask) - 1;
         }
-        far = nxt;
+        far = nxt < 0 ? 0 : nxt;                                      // no lane equals the maximum (a non-finite coordinate): the values are unspecified, the index stays in [0, n)
     }
 }
 template <int PPT>
@@ -120,7 +120,7 @@ inline void launch_pn2_fps(const FpsParams& p, int B, hipStream_t s) {
 
 // ---- ball query + grouping: one wave per centroid.  The wave scans the cloud 64 points at a time in index order; a ballot and
 // a prefix pop-count give every in-ball point its slot, so the group is the first `nsample` in-ball indices (padded with the
-// first).  The rows of the grouped matrix [ (centroid, sample), 3 + C ] = [xyz - centroid | features] are then written with the
+// first; a ball with no point in it is filled with point 0).  The rows of the grouped matrix [ (centroid, sample), 3 + C ] = [xyz - centroid | features] are then written with the
 // channel index on the lanes.
 constexpr int PN2_MAX_NSAMPLE = 64;
 struct GroupParams {
@@ -150,6 +150,7 @@ __global__ __launch_bounds__(256) void pn2_group_kernel(const GroupParams p) { f
         cnt += __popcll(mask);
     }
     if (cnt > p.nsample) cnt = p.nsample;
+    if (cnt == 0 && lane == 0) s_idx[wave][0] = 0;            // an empty ball (a centroid farther than the radius from every point, or a non-finite one) is filled with point 0
     wave_sync();
     if (lane < p.nsample && (!shared || wave == 0)) {
         const int src = s_idx[wave][lane < cnt ? lane : 0];
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(256) void pn2_interp_kernel(const InterpParams p) {
             const float ov = __shfl_xor(best, m); const int oi = __shfl_xor(besti, m);
             if (ov < best || (ov == best && oi < besti)) { best = ov; besti = oi; }
         }
+        if (besti >= p.s) besti = 0;                                  // no distance below INF (non-finite coordinates): the values are unspecified, the index stays in [0, s)
         nn[r] = besti;
         w[r] = 1.0f / (best + 1e-8f);
         ACH_UNROLL

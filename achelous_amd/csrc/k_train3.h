@@ -51,6 +51,7 @@ static __global__ __launch_bounds__(256) void train_pn2_interp_bwd_kernel(const 
             const float ov = __shfl_xor(best, m); const int oi = __shfl_xor(besti, m);
             if (ov < best || (ov == best && oi < besti)) { best = ov; besti = oi; }
         }
+        if (besti >= p.s) besti = 0;                                  // as the forward kernel: never an index outside [0, s)
         nn[r] = besti;
         w[r] = 1.0f / (best + 1e-8f);
         ACH_UNROLL

@@ -18,7 +18,8 @@ that index selection can be compared BIT-EXACTLY between this file and the HIP k
   * every squared distance is the direct form ((dx*dx + dy*dy) + dz*dz) in fp32 with one rounding per operation and no
     fused multiply-add (the published code uses the expanded |a|^2 + |b|^2 - 2ab matrix form);
   * a point is inside a ball iff d <= fp32(radius^2); a group holds the first `nsample` such points in index order and
-    is padded with the first of them;
+    is padded with the first of them; an EMPTY ball (a centroid farther than the radius from every point) is filled with
+    point 0;
   * the three nearest neighbours are those of a stable sort of the distances (ties to the lowest index).
 """
 import numpy as np
@@ -72,14 +73,14 @@ def farthest_point_sample(xyz, npoint):
 
 
 def ball_query(radius, nsample, xyz, new_xyz):
-    """-> int32 [s, nsample]: first nsample indices (ascending) with d <= radius^2, padded with the first."""
+    """-> int32 [s, nsample]: first nsample indices (ascending) with d <= radius^2, padded with the first; all 0 for an empty ball."""
     r2 = f32(radius * radius)
     d = sqdist(new_xyz, xyz)
     out = np.zeros((new_xyz.shape[0], nsample), np.int32)
     for s in range(new_xyz.shape[0]):
         idx = np.nonzero(d[s] <= r2)[0][:nsample]
         out[s, :len(idx)] = idx
-        out[s, len(idx):] = idx[0]
+        out[s, len(idx):] = idx[0] if len(idx) else 0        # an empty ball is filled with point 0
     return out
 
 

@@ -322,7 +322,8 @@ REPLAY_REFERENCES = {
     'avgpool3': lambda x: F.avg_pool2d(x, 3, 1, 1),
     'deform_conv3x3': lambda x, offset, mask, weight, stride=1, pad=1: ref_deform_conv(x, offset, mask, weight, stride, pad),
 }
-# reached by train_graph.py, not replayed: the PointNet++ set abstraction (integer indices out, coordinates in: tests/test_pointnet2.py), which EN-GDF-PN does not run
+# reached by train_graph.py, not replayed: the PointNet++ geometry (integer indices out, coordinates in), which EN-GDF-PN does not run — each primitive is held against the
+# oracle directly, forward and adjoint, in tests/test_pn2_geometry.py (the whole branch in tests/test_pointnet2.py)
 REPLAY_NOT_COVERED = {'pn2_fps', 'pn2_group', 'pn2_interp'}
 
 
