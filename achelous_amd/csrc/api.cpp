@@ -16,6 +16,7 @@
 #include "k_train3.h"
 #include "k_loss.h"
 #include "k_metrics.h"
+#include "k_data.h"
 
 struct ach_handle {
     ach::EngineBase* eng = nullptr;
@@ -856,6 +857,100 @@ int ach_eval_match(const float* rows, const int32_t* counts, int32_t yx_order, i
         for (int t = 0; t < T; ++t) p.thr[t] = thresholds[t];
         p.flags = flags; p.match = match; p.iou = iou; p.score = score; p.gt_per_class = reinterpret_cast<unsigned long long*>(gt_per_class);
         ACH_LAUNCH(ach::match_kernel, dim3(unsigned(B)), dim3(256), static_cast<hipStream_t>(stream), p);
+    });
+}
+
+// ---- training batches from ragged frames (k_data.h).  Both entries check the host copy of the frame table — every extent against its arena, every table
+// offset against `tabs`, every bounds / index entry the kernels will follow — BEFORE anything is launched; a bad table is ACH_ERR_INVALID and no launch.
+static void data_need_bounds(const int32_t* tabs, int64_t tabs_len, int64_t boff, int64_t koff, int64_t ks, int64_t n_out, int64_t n_in, const char* what) {
+    train_need(ks >= 1 && boff >= 0 && koff >= 0 && n_out <= (tabs_len - boff) / 2 && boff + 2 * n_out <= tabs_len && n_out <= (tabs_len - koff) / ks &&
+               koff + n_out * ks <= tabs_len, what);
+}
+int ach_data_letterbox_batch(const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const int32_t* tabs_host,
+                             const int32_t* tabs_dev, int64_t tabs_len, const float* lut, int32_t B, int32_t R, uint8_t* mid, int64_t mid_bytes, void* out,
+                             int32_t out_kind, void* stream) {
+    return train_guard([&] {
+        train_need(arena && table_host && table_dev && tabs_host && tabs_dev && mid && out && B > 0 && R > 0 && R <= 16384 && tabs_len >= 0 && mid_bytes >= 0,
+                   "ach_data_letterbox_batch");
+        train_need(out_kind >= ach::DATA_F32 && out_kind <= ach::DATA_U8_HWC && (lut || out_kind == ach::DATA_U8_HWC), "ach_data_letterbox_batch: out_kind 0..3, a value table unless 3");
+        train_need(arena_bytes > 0 && arena_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(arena) & 15u) == 0 && (reinterpret_cast<uintptr_t>(mid) & 3u) == 0,
+                   "ach_data_letterbox_batch: the image arena is 16-byte aligned and padded to 16 bytes");
+        const int R4 = (R + 3) / 4 * 4;
+        long max_span = 0, max_rows = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t* f = table_host + long(b) * ach::DATA_TABLE_COLS;
+            const int64_t off = f[0], H = f[1], W = f[2], pitch = f[3], nw = f[4], nh = f[5], dx = f[6], dy = f[7];
+            train_need(H >= 1 && W >= 1 && H < (1L << 30) && W < (1L << 30) && pitch >= 3 * W && pitch < (1L << 32) && off >= 0 && off <= arena_bytes &&
+                       (H - 1) * pitch + 3 * W <= arena_bytes - off, "ach_data_letterbox_batch: a frame's extent passes the image arena");
+            train_need(nw >= 1 && nh >= 1 && nw < (1L << 30) && nh < (1L << 30) && dx > -(1L << 30) && dx < (1L << 30) && dy > -(1L << 30) && dy < (1L << 30),
+                       "ach_data_letterbox_batch: placement out of range");
+            data_need_bounds(tabs_host, tabs_len, f[8], f[9], f[10], nw, W, "ach_data_letterbox_batch: a horizontal table offset passes the table buffer");
+            data_need_bounds(tabs_host, tabs_len, f[11], f[12], f[13], nh, H, "ach_data_letterbox_batch: a vertical table offset passes the table buffer");
+            const ach::DataWindow w = ach::data_window(nw, nh, dx, dy, R);
+            if (w.vx0 >= w.vx1 || w.vy0 >= w.vy1) continue;
+            // the entries the kernels follow: inside the source axis, at most ks taps, both ends non-decreasing (the staged range is [first of the first, end of the last))
+            auto walk = [&](int64_t boff, int64_t ks, long lo, long hi, int64_t n_in, long& first0, long& end1) {
+                long pf = 0, pe = 0;
+                for (long o = lo; o < hi; ++o) {
+                    const long first = tabs_host[boff + 2 * o], count = tabs_host[boff + 2 * o + 1];
+                    train_need(first >= 0 && count >= 0 && count <= ks && first + count <= n_in && (o == lo || (first >= pf && first + count >= pe)),
+                               "ach_data_letterbox_batch: a bounds entry leaves its source axis");
+                    pf = first; pe = first + count;
+                    if (o == lo) first0 = first;
+                }
+                end1 = pe;
+            };
+            long sx0 = 0, sx1 = 0, r0 = 0, r1 = 0;
+            walk(f[8], f[10], w.vx0 - dx, w.vx1 - dx, W, sx0, sx1);
+            walk(f[11], f[13], w.vy0 - dy, w.vy1 - dy, H, r0, r1);
+            train_need(f[14] >= 0 && f[14] % 4 == 0 && f[14] <= mid_bytes && (r1 - r0) * 3 * R4 <= mid_bytes - f[14],
+                       "ach_data_letterbox_batch: a frame's intermediate passes the intermediate arena");
+            max_span = std::max(max_span, (sx1 - sx0) * 3);
+            max_rows = std::max(max_rows, r1 - r0);
+        }
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (max_rows > 0 && max_span > 0) {
+            const long lstride = (max_span + 15 + 15) / 16 * 16;
+            if (lstride > ach::DATA_LDS_BYTES) throw ach::AchError{ACH_ERR_UNSUPPORTED, "ach_data_letterbox_batch: a frame needs more than 16379 source columns of one row"};
+            const int rows_pb = int(std::min<long>(ach::DATA_ROWS, ach::DATA_LDS_BYTES / lstride));
+            ach::DataHParams hp{arena, reinterpret_cast<const long long*>(table_dev), tabs_dev, mid, R, R4, rows_pb, int(lstride)};
+            ACH_LAUNCH(ach::data_hpass_kernel, dim3(unsigned(ach::cdivl(max_rows, rows_pb)), unsigned(B)), dim3(256), s, hp);
+        }
+        ach::DataVParams vp{reinterpret_cast<const long long*>(table_dev), tabs_dev, mid, lut, out, R, R4};
+        const dim3 grid(unsigned(ach::cdivl(long(R) * (R4 / 4), 256)), unsigned(B));
+        if (out_kind == ach::DATA_F32) ACH_LAUNCH(ach::data_vpass_kernel<float>, grid, dim3(256), s, vp);
+        else if (out_kind == ach::DATA_BF16) ACH_LAUNCH(ach::data_vpass_kernel<ach::bf16_t>, grid, dim3(256), s, vp);
+        else if (out_kind == ach::DATA_F16) ACH_LAUNCH(ach::data_vpass_kernel<ach::f16_t>, grid, dim3(256), s, vp);
+        else ACH_LAUNCH(ach::data_vpass_kernel<uint8_t>, grid, dim3(256), s, vp);
+    });
+}
+int ach_data_labels_batch(const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const int32_t* tabs_host,
+                          const int32_t* tabs_dev, int64_t tabs_len, int32_t B, int32_t R, int32_t num_classes_seg, void* png, void* png_w, int32_t label_kind,
+                          void* stream) {
+    return train_guard([&] {
+        train_need(arena && table_host && table_dev && tabs_host && tabs_dev && png && png_w && B > 0 && B <= 65535 && R > 0 && R <= 16384 && tabs_len >= 0 &&
+                   arena_bytes >= 0, "ach_data_labels_batch");
+        train_need(num_classes_seg >= 0 && num_classes_seg <= 255 && (label_kind == 0 || label_kind == 2), "ach_data_labels_batch: classes 0..255, label_kind 0 (int64) or 2 (uint8)");
+        for (int b = 0; b < B; ++b) {
+            const int64_t* f = table_host + long(b) * ach::DATA_TABLE_COLS;
+            const int64_t nw = f[0], nh = f[1], dx = f[2], dy = f[3];
+            train_need(nw >= 1 && nh >= 1 && nw < (1L << 30) && nh < (1L << 30) && dx > -(1L << 30) && dx < (1L << 30) && dy > -(1L << 30) && dy < (1L << 30),
+                       "ach_data_labels_batch: placement out of range");
+            const ach::DataWindow w = ach::data_window(nw, nh, dx, dy, R);
+            for (int m = 0; m < 2; ++m) {
+                const int64_t* g = f + 4 + 6 * m;
+                if (g[0] < 0) continue;
+                const int64_t off = g[0], H = g[1], W = g[2], pitch = g[3];
+                train_need(H >= 1 && W >= 1 && H < (1L << 30) && W < (1L << 30) && pitch >= W && pitch < (1L << 32) && off <= arena_bytes &&
+                           (H - 1) * pitch + W <= arena_bytes - off, "ach_data_labels_batch: a label map's extent passes the label arena");
+                train_need(g[4] >= 0 && g[5] >= 0 && nw <= tabs_len - g[4] && nh <= tabs_len - g[5], "ach_data_labels_batch: an index table offset passes the table buffer");
+                if (w.vx0 >= w.vx1 || w.vy0 >= w.vy1) continue;
+                for (long o = w.vx0 - dx; o < w.vx1 - dx; ++o) train_need(tabs_host[g[4] + o] >= -1 && tabs_host[g[4] + o] < W, "ach_data_labels_batch: a column index leaves its map");
+                for (long o = w.vy0 - dy; o < w.vy1 - dy; ++o) train_need(tabs_host[g[5] + o] >= -1 && tabs_host[g[5] + o] < H, "ach_data_labels_batch: a row index leaves its map");
+            }
+        }
+        ach::DataLabelParams lp{arena, reinterpret_cast<const long long*>(table_dev), tabs_dev, {png, png_w}, R, num_classes_seg, label_kind == 0 ? 1 : 0};
+        ACH_LAUNCH(ach::data_labels_kernel, dim3(unsigned(ach::cdivl(long(R) * R, 256)), 2u, unsigned(B)), dim3(256), static_cast<hipStream_t>(stream), lp);
     });
 }
 

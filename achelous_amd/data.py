@@ -1,0 +1,397 @@
+"""Training batches assembled on the device from ragged frames (csrc/k_data.h; C ABI `ach_data_letterbox_batch`, `ach_data_labels_batch`).
+
+The live path of the reference's `YoloDataset.__getitem__` / `get_random_data` + `yolo_dataset_collate_all` (utils/dataloader.py:87-148, 153-233, 517-550) for B decoded
+frames of different sizes at once, producing what `GraphedTrainStep` / `MultiTaskLoss.forward(outputs, boxes, counts, png, png_w, pc_labels)` and the network take:
+
+    images  [B, 3, R, R] fp32 / bf16 / fp16   PIL BICUBIC resize to (nw, nh) pasted at (dx, dy) on a (128, 128, 128) canvas, ((v / 255) - mean) / std in float64
+                                              rounded once to fp32 (a 768-entry table), then one RNE rounding to a 16-bit type; `torch.uint8`: the bytes, [B, R, R, 3]
+    png, png_w [B, R, R] uint8 / int64        PIL NEAREST resize, pasted on zeros, min(v, num_classes_seg) / min(v, 2); a frame without a water-line map: zeros
+    boxes [B, G, 5] fp32, counts [B] int32    the reference's integer box arithmetic in numpy on the host (a handful of numbers), packed as `losses.pack_labels` packs
+    points [B, D, N], pc_labels [B, N] int64  N rows sampled with replacement on the host, then the existing `prepost.normalize_points`
+    radar   [B, C, R, R] fp32                 passes through
+
+Per batch: two image launches, one label launch, one point launch, whatever B is; three host-to-device copies (image arena, label arena, one buffer with the frame
+tables, the coefficient / index tables, the value table, boxes, points and radar maps) from reusable pinned memory, none back.  Placement defaults to the
+reference's letterbox; a caller may pass any `(nw, nh, dx, dy)` per frame (scale / position jitter): the paste clips as `Image.paste` does.  Not covered: flips, the
+HSV jitter / mosaic / mixup of the reference's unreachable code, image decoding, the float one-hot targets (the losses take integer maps).
+No torch-op or CPU fallback: without the HIP library these raise.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import prepost as _pp
+from .losses import pack_labels
+from .train_ops import _lib, _p, _stream
+
+TABLE_COLS = 16          # DATA_TABLE_COLS of k_data.h
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+_OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
+_LABEL_KIND = {torch.int64: 0, torch.uint8: 2}
+_ERRORS = {-1: ValueError, -2: NotImplementedError}
+
+Batch = collections.namedtuple('Batch', 'images radar points boxes counts png png_w pc_labels')
+Arena = collections.namedtuple('Arena', 'data frames')          # data: 1-D uint8 tensor on the device; frames: per frame (byte offset, H, W, pitch) or None
+
+
+def _check(lib, rc):
+    if rc != 0:
+        raise _ERRORS.get(rc, RuntimeError)((lib.lib.ach_last_error(None) or b'data kernel failed').decode())
+
+
+# ------------------------------------------------------------------------------------------------------------------ host rules
+def value_table():
+    """[3, 256] fp32: ((v / 255) - mean) / std in float64, rounded once (utils/dataloader.py:105 with utils_seg/utils.py:40-44, then FloatTensor)"""
+    v = np.arange(256, dtype=np.float64)
+    return np.stack([(v / 255.0 - m) / s for m, s in zip(MEAN, STD)]).astype(np.float32)
+
+
+_NEAREST, _BICUBIC = {}, {}
+
+
+def nearest_index(in_size, out_size):
+    """Source index of every output sample of PIL's Image.NEAREST resize along one axis: Pillow's running sum in double (a = in / out; xx = a / 2; index =
+    int(xx); xx += a), which `floor((x + 0.5) * in / out)` does not reproduce.  -1: past the axis (left zero).  int32 [out_size], cached."""
+    key = (int(in_size), int(out_size))
+    if key not in _NEAREST:
+        a = key[0] / key[1]
+        xx = 0.5 * a
+        idx = np.empty(key[1], np.int32)
+        for x in range(key[1]):
+            i = int(xx)
+            idx[x] = i if i < key[0] else -1
+            xx += a
+        _NEAREST[key] = idx
+    return _NEAREST[key]
+
+
+def _bicubic_tables(in_size, out_size):
+    key = (int(in_size), int(out_size))
+    if key not in _BICUBIC:
+        b, k, ks = _pp._pil_coeffs(key[0], key[1], 'cpu')
+        assert int(k.abs().max()) < 1 << 23                  # the kernels multiply taps as 24-bit integers (k_data.h tap_mul)
+        _BICUBIC[key] = (b.numpy().reshape(-1), k.numpy().reshape(-1), int(ks))
+    return _BICUBIC[key]
+
+
+def default_placement(iw, ih, resolution):
+    """the reference's letterbox (utils/dataloader.py:178-182): (nw, nh, dx, dy)"""
+    R = int(resolution)
+    scale = min(R / iw, R / ih)
+    nw, nh = int(iw * scale), int(ih * scale)
+    return nw, nh, (R - nw) // 2, (R - nh) // 2
+
+
+def adjust_boxes(boxes, iw, ih, placement, resolution):
+    """utils/dataloader.py:219-228 and :108-110 for one frame: integer corners (x1, y1, x2, y2, class) of the original image -> float64 [n, 5] (cx, cy, w, h, class)
+    on the canvas.  The scaled corners are truncated toward zero when they are stored back into the integer array; input order is kept."""
+    box = np.array(boxes, dtype=np.int64).reshape(-1, 5)
+    nw, nh, dx, dy = (int(v) for v in placement)
+    R = int(resolution)
+    if len(box):
+        box[:, [0, 2]] = box[:, [0, 2]] * nw / iw + dx
+        box[:, [1, 3]] = box[:, [1, 3]] * nh / ih + dy
+        box[:, 0:2] = np.maximum(box[:, 0:2], 0)
+        box[:, 2:4] = np.minimum(box[:, 2:4], R)
+        box = box[(box[:, 2] - box[:, 0] > 1) & (box[:, 3] - box[:, 1] > 1)]
+    out = box.astype(np.float64)
+    if len(out):
+        out[:, 2:4] -= out[:, 0:2]
+        out[:, 0:2] += out[:, 2:4] / 2
+    return out
+
+
+def sample_points(clouds, labels, num_points, indices=None, rng=None):
+    """utils/dataloader.py:137-140: `num_points` rows with replacement from each ragged cloud [n_i, D] -> (fp32 [B, N, D], int64 [B, N], the indices [B, N])."""
+    N = int(num_points)
+    if indices is None and rng is None:
+        raise ValueError("sample_points: pass `indices` [B, N] or a numpy.random.Generator as `rng`")
+    pts, lab, used = [], [], []
+    for b, cloud in enumerate(clouds):
+        c = np.asarray(cloud)
+        if c.ndim != 2 or c.shape[0] == 0:
+            raise ValueError(f"sample_points: frame {b} has an empty point cloud")
+        idx = np.asarray(indices[b], dtype=np.int64) if indices is not None else rng.choice(c.shape[0], N, replace=True)
+        if idx.shape != (N,) or idx.min() < 0 or idx.max() >= c.shape[0]:
+            raise ValueError(f"sample_points: frame {b} needs {N} indices below {c.shape[0]}")
+        pts.append(c[idx].astype(np.float32))
+        lab.append(np.asarray(labels[b])[idx].astype(np.int64))
+        used.append(idx)
+    return np.stack(pts), np.stack(lab), np.stack(used)
+
+
+# ------------------------------------------------------------------------------------------------------------------ staging
+def _host_array(a, channels):
+    a = a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    want = 3 if channels == 3 else 2
+    if a.dtype != np.uint8 or a.ndim != want or (channels == 3 and a.shape[2] != 3) or a.size == 0:
+        raise TypeError("frames are CPU uint8 arrays / tensors: images [H, W, 3], label maps [H, W]")
+    return a
+
+
+class _Pinned:
+    """Reusable pinned staging memory per device.  A buffer is written again only after the copy that read it has completed (an event QUERY, never a wait); while
+    it is in flight another buffer is taken, so nothing here synchronises."""
+
+    def __init__(self, device):
+        self.device, self.slots = device, {}
+
+    def take(self, name, nbytes):
+        if self.device.type != 'cuda':
+            return [torch.empty(max(nbytes, 16), dtype=torch.uint8), None]
+        ring = self.slots.setdefault(name, [])
+        for slot in ring:
+            if slot[0].numel() >= nbytes and (slot[1] is None or slot[1].query()):
+                return slot
+        ring[:] = [s for s in ring if s[0].numel() >= nbytes][-3:]
+        slot = [torch.empty(max(16, nbytes + nbytes // 8), dtype=torch.uint8, pin_memory=True), None]
+        ring.append(slot)
+        return slot
+
+    def upload(self, slot, nbytes):
+        if self.device.type != 'cuda':
+            return slot[0][:nbytes]
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        dev.copy_(slot[0][:nbytes], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(self.device))
+        return dev
+
+
+_PINNED = {}
+
+
+def _pinned(device):
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if device not in _PINNED:
+        _PINNED[device] = _Pinned(device)
+    return _PINNED[device]
+
+
+def pack_arena(frames, channels=3, device='cuda', name=None):
+    """A list of CPU uint8 arrays / tensors (None: the frame has no such map) -> `Arena`: packed into reusable pinned memory, 16-byte aligned frames, ONE copy."""
+    pin = _pinned(device)
+    arrs = [None if f is None else _host_array(f, channels) for f in frames]
+    offs, total = [], 0
+    for a in arrs:
+        offs.append(total)
+        if a is not None:
+            total += (a.size + 15) // 16 * 16
+    total = max(total, 16)
+    slot = pin.take(name or f'arena{channels}', total)
+    host = slot[0].numpy()
+    for a, o in zip(arrs, offs):
+        if a is not None:
+            np.copyto(host[o:o + a.size].reshape(a.shape), a)
+    data = pin.upload(slot, total)
+    return Arena(data, [None if a is None else (o, a.shape[0], a.shape[1], a.shape[1] * channels) for a, o in zip(arrs, offs)])
+
+
+class _Meta:
+    """Everything small a batch needs on the device, in ONE pinned buffer and one non-blocking copy: frame tables, coefficient / index tables (each distinct
+    (in, out) pair once), the value table, boxes, points, radar maps."""
+
+    def __init__(self, device, name='meta'):
+        self.pin, self.parts, self.nbytes, self.name = _pinned(device), [], 0, name          # a `_Meta` kept across batches needs a `name` of its own
+        self.tabs, self.tab_at, self.tab_len = [], {}, 0
+        self.slot = self.dev = None
+
+    def add(self, arr):
+        arr = np.ascontiguousarray(arr)
+        off = self.nbytes
+        self.parts.append((off, arr))
+        self.nbytes += (arr.nbytes + 15) // 16 * 16
+        return (off, arr.dtype, arr.shape)
+
+    def table(self, key, arr):
+        if key not in self.tab_at:
+            self.tab_at[key] = self.tab_len
+            self.tabs.append(np.ascontiguousarray(arr, dtype=np.int32).reshape(-1))
+            self.tab_len += self.tabs[-1].size
+        return self.tab_at[key]
+
+    def commit(self):
+        self.tabs_ref = self.add(np.concatenate(self.tabs) if self.tabs else np.zeros(1, np.int32))
+        self.slot = self.pin.take(self.name, self.nbytes)
+        host = self.slot[0].numpy()
+        for off, arr in self.parts:
+            host[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+        self.dev = self.pin.upload(self.slot, self.nbytes)
+
+    def host_ptr(self, ref):
+        return ctypes.c_void_p(self.slot[0].data_ptr() + ref[0])
+
+    def dev_ptr(self, ref):
+        return ctypes.c_void_p(self.dev.data_ptr() + ref[0])
+
+    def tensor(self, ref):
+        off, dtype, shape = ref
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return self.dev[off:off + n].view(getattr(torch, np.dtype(dtype).name)).view(shape)
+
+
+def _as_arena(frames, channels, device, name):
+    return frames if isinstance(frames, Arena) else pack_arena(frames, channels, device, name)
+
+
+def _placements(frames, placements, R):
+    if placements is None:
+        return [default_placement(f[2], f[1], R) for f in frames]
+    out = [tuple(int(v) for v in p) for p in placements]
+    if len(out) != len(frames) or any(len(p) != 4 or p[0] < 1 or p[1] < 1 for p in out):
+        raise ValueError("placements: one (nw, nh, dx, dy) per frame with nw, nh >= 1")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ the two launches
+def _plan_images(meta, arena, places, R):
+    R4 = (R + 3) // 4 * 4
+    table = np.zeros((len(arena.frames), TABLE_COLS), np.int64)
+    mid = 0
+    for b, (fr, (nw, nh, dx, dy)) in enumerate(zip(arena.frames, places)):
+        off, H, W, pitch = fr
+        hb, hk, hks = _bicubic_tables(W, nw)
+        vb, vk, vks = _bicubic_tables(H, nh)
+        table[b] = (off, H, W, pitch, nw, nh, dx, dy, meta.table(('hb', W, nw), hb), meta.table(('hk', W, nw), hk), hks,
+                    meta.table(('hb', H, nh), vb), meta.table(('hk', H, nh), vk), vks, mid, 0)
+        y0, y1 = min(max(dy, 0), R), min(max(dy + nh, 0), R)
+        if y0 < y1 and min(max(dx, 0), R) < min(max(dx + nw, 0), R):
+            rows = int(vb[2 * (y1 - 1 - dy)] + vb[2 * (y1 - 1 - dy) + 1] - vb[2 * (y0 - dy)])
+            mid += rows * 3 * R4
+    return meta.add(table), max(mid, 16)
+
+
+def _launch_images(meta, arena, ref, mid_bytes, lut_ref, R, dtype):
+    data = arena.data
+    lib = _lib(data)
+    B = len(arena.frames)
+    mid = torch.empty(mid_bytes, dtype=torch.uint8, device=data.device)
+    out = torch.empty((B, R, R, 3) if dtype == torch.uint8 else (B, 3, R, R), dtype=dtype, device=data.device)
+    _check(lib, lib.lib.ach_data_letterbox_batch(_p(data), data.numel(), meta.host_ptr(ref), meta.dev_ptr(ref), meta.host_ptr(meta.tabs_ref), meta.dev_ptr(meta.tabs_ref),
+                                                 meta.tab_len, meta.dev_ptr(lut_ref), B, R, _p(mid), mid_bytes, _p(out), _OUT_KIND[dtype], _stream(data)))
+    return out
+
+
+def _plan_labels(meta, arena, arena_w, places, R):
+    """both maps of a frame live in ONE arena: `arena.frames` then `arena_w.frames` index the same `data`"""
+    B = len(arena.frames)
+    table = np.zeros((B, TABLE_COLS), np.int64)
+    for b, (nw, nh, dx, dy) in enumerate(places):
+        table[b, :4] = (nw, nh, dx, dy)
+        for m, fr in enumerate((arena.frames[b], arena_w.frames[b])):
+            if fr is None:
+                table[b, 4 + 6 * m] = -1
+                continue
+            off, H, W, pitch = fr
+            table[b, 4 + 6 * m:10 + 6 * m] = (off, H, W, pitch, meta.table(('nn', W, nw), nearest_index(W, nw)), meta.table(('nn', H, nh), nearest_index(H, nh)))
+    return meta.add(table)
+
+
+def _launch_labels(meta, data, ref, B, R, num_classes_seg, label_dtype):
+    lib = _lib(data)
+    png = torch.empty(B, R, R, dtype=label_dtype, device=data.device)
+    png_w = torch.empty(B, R, R, dtype=label_dtype, device=data.device)
+    _check(lib, lib.lib.ach_data_labels_batch(_p(data), data.numel(), meta.host_ptr(ref), meta.dev_ptr(ref), meta.host_ptr(meta.tabs_ref), meta.dev_ptr(meta.tabs_ref),
+                                              meta.tab_len, B, R, int(num_classes_seg), _p(png), _p(png_w), _LABEL_KIND[label_dtype], _stream(data)))
+    return png, png_w
+
+
+def _pack_label_arena(png, png_w, device):
+    n = len(png)
+    both = pack_arena(list(png) + list(png_w), 1, device, 'labels')
+    if any(f is None for f in both.frames[:n]):
+        raise ValueError("every frame needs a semantic label map (only the water-line map may be missing)")
+    return Arena(both.data, both.frames[:n]), Arena(both.data, both.frames[n:])
+
+
+def _image_dtype(dtype):
+    if dtype not in _OUT_KIND:
+        raise TypeError(f"images are float32, bfloat16, float16 or uint8 (the bytes, HWC), got {dtype}")
+    return dtype
+
+
+def letterbox_batch(images, resolution, placements=None, dtype=torch.float32, device='cuda'):
+    """`images`: a list of CPU uint8 [H, W, 3] arrays / tensors of any sizes, or an `Arena` already on the device -> [B, 3, R, R] `dtype` (torch.uint8: [B, R, R, 3],
+    byte for byte `prepost.resize_image`).  Two launches for the whole batch."""
+    R = int(resolution)
+    arena = _as_arena(images, 3, device, 'images')
+    places = _placements(arena.frames, placements, R)
+    meta = _Meta(arena.data.device)
+    ref, mid_bytes = _plan_images(meta, arena, places, R)
+    lut = meta.add(value_table())
+    meta.commit()
+    return _launch_images(meta, arena, ref, mid_bytes, lut, R, _image_dtype(dtype))
+
+
+def labels_batch(png, png_w, resolution, num_classes_seg, placements=None, label_dtype=torch.uint8, device='cuda'):
+    """`png`, `png_w`: lists of CPU uint8 [H, W] label maps (`png_w[b]` may be None), or two `Arena`s over one device buffer -> (png, png_w) [B, R, R] `label_dtype`
+    (uint8 or int64).  One launch.  Default placement: the reference's letterbox of the semantic map's size."""
+    if label_dtype not in _LABEL_KIND:
+        raise TypeError(f"label maps are uint8 or int64, got {label_dtype}")
+    R = int(resolution)
+    a, aw = (png, png_w) if isinstance(png, Arena) else _pack_label_arena(png, png_w, device)
+    places = _placements(a.frames, placements, R)
+    meta = _Meta(a.data.device)
+    ref = _plan_labels(meta, a, aw, places, R)
+    meta.commit()
+    return _launch_labels(meta, a.data, ref, len(a.frames), R, num_classes_seg, label_dtype)
+
+
+def _normalize_points(points, dtype):
+    lib = getattr(_lib, 'test_library', None)
+    if lib is None:
+        return _pp.normalize_points(points, dtype)
+    from . import engine as _eng                         # tests: the same kernel under the emulation library
+    code = {torch.float32: _eng.DTYPE_F32, torch.bfloat16: _eng.DTYPE_BF16, torch.float16: _eng.DTYPE_F16}[dtype]
+    h = _eng.NativeEngine(lib, num_det=1, num_seg=1, phi='S0', backbone='en', resolution=32, pc_channels=3, pc_classes=1, num_points=16, nano_head=True, spp=True, dtype=code)
+    B, N, D = points.shape
+    out = torch.empty(B, D, N, dtype=dtype, device=points.device)
+    h.normalize_points(B, N, D, points.contiguous(), out)
+    return out
+
+
+class TrainBatcher:
+    """`TrainBatcher(resolution, num_classes_seg, num_points)(frames)` -> `Batch(images, radar, points, boxes, counts, png, png_w, pc_labels)` on `device`.
+
+    `frames`: a list of dicts with `image` [H, W, 3] uint8, `png` [H, W] uint8, optionally `png_w` [H, W] uint8 (absent / None: zeros), `boxes` [n, 5] integers
+    (x1, y1, x2, y2, class) in pixels of the original image, `radar` [C, R, R], and `points` [n, D] with `point_labels` [n] (all frames or none).  `placements`: one
+    (nw, nh, dx, dy) per frame instead of the reference's letterbox.  Points are sampled with the caller's `indices` [B, N] or drawn from `rng`
+    (a numpy.random.Generator).  `max_boxes` fixes G (a captured graph needs fixed shapes); more surviving boxes than that is `pack_labels`' error."""
+
+    def __init__(self, resolution, num_classes_seg, num_points=512, dtype=torch.float32, label_dtype=torch.uint8, max_boxes=None, device='cuda'):
+        if label_dtype not in _LABEL_KIND:
+            raise TypeError(f"label maps are uint8 or int64, got {label_dtype}")
+        self.R, self.num_classes_seg, self.num_points = int(resolution), int(num_classes_seg), int(num_points)
+        self.dtype, self.label_dtype, self.max_boxes, self.device = _image_dtype(dtype), label_dtype, max_boxes, device
+        self.point_dtype = torch.float32 if dtype == torch.uint8 else dtype
+
+    def __call__(self, frames, placements=None, indices=None, rng=None):
+        R, B = self.R, len(frames)
+        if B == 0:
+            raise ValueError("TrainBatcher: an empty batch")
+        arena = pack_arena([f['image'] for f in frames], 3, self.device, 'images')
+        la, law = _pack_label_arena([f['png'] for f in frames], [f.get('png_w') for f in frames], self.device)
+        places = _placements(arena.frames, placements, R)
+        meta = _Meta(arena.data.device)
+        iref, mid_bytes = _plan_images(meta, arena, places, R)
+        lref = _plan_labels(meta, la, law, places, R)
+        lut = meta.add(value_table())
+        per = [torch.from_numpy(adjust_boxes(f.get('boxes', ()), fr[2], fr[1], p, R)) for f, fr, p in zip(frames, arena.frames, places)]
+        boxes, counts = pack_labels(per, self.max_boxes, device='cpu')
+        bref, cref = meta.add(boxes.numpy()), meta.add(counts.numpy())
+        pref = plref = rref = None
+        if any(f.get('points') is not None for f in frames):
+            pts, plab, _ = sample_points([f.get('points', ()) for f in frames], [f.get('point_labels') for f in frames], self.num_points, indices, rng)
+            pref, plref = meta.add(pts), meta.add(plab)
+        if any(f.get('radar') is not None for f in frames):
+            rref = meta.add(np.stack([np.asarray(f['radar']) for f in frames]).astype(np.float32))
+        meta.commit()
+        images = _launch_images(meta, arena, iref, mid_bytes, lut, R, self.dtype)
+        png, png_w = _launch_labels(meta, la.data, lref, B, R, self.num_classes_seg, self.label_dtype)
+        points = _normalize_points(meta.tensor(pref), self.point_dtype) if pref is not None else None
+        return Batch(images, meta.tensor(rref) if rref is not None else None, points, meta.tensor(bref), meta.tensor(cref), png, png_w,
+                     meta.tensor(plref) if plref is not None else None)

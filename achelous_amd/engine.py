@@ -41,7 +41,7 @@ class NativeLibrary:
                'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
                'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
                'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss',
-               'ach_eval_confusion', 'ach_eval_match')
+               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch')
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -145,7 +145,9 @@ class NativeLibrary:
                            ('ach_train_loss_scale', [vp, vp, vp, i64, vp]),
                            ('ach_train_seg_loss', [vp, vp, i32, vp, i32, i32, i64, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
                            ('ach_eval_confusion', [vp, i32, i32, vp, i32, i32, i32, i64, vp, vp]),
-                           ('ach_eval_match', [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp])):
+                           ('ach_eval_match', [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+                           ('ach_data_letterbox_batch', [vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, i64, vp, i32, vp]),
+                           ('ach_data_labels_batch', [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, vp])):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = ctypes.c_int
         L.ach_record_words.argtypes = [i32, i32]

@@ -397,6 +397,31 @@ int ach_eval_match(const float* rows, const int32_t* counts, int32_t yx_order, i
                    int32_t B, int32_t max_det, int32_t G, int32_t C, const double* thresholds, int32_t T, uint8_t* flags, int32_t* match, double* iou, float* score,
                    uint64_t* gt_per_class, void* stream);
 
+/* Training batches assembled on the device from ragged frames (achelous_amd/csrc/k_data.h; achelous_amd/data.py): the reference's dataset step
+ * (utils/dataloader.py:87-148, 153-233) for a whole batch, with a launch count that does not depend on the batch and no device-to-host copy.
+ * All images sit in one packed uint8 arena (HWC rows), all label maps in another; frames are described by a host-built int64 table of 16 columns per frame
+ * whose copy on the device the kernels read.  `tabs` is one int32 buffer holding every bounds / coefficient / index table; table offsets count its elements.
+ * Both entries read the HOST copies (`table_host`, `tabs_host`) first and check every extent against its arena, every table offset against `tabs_len` and every
+ * table entry the kernels will follow against its source axis: a bad table returns ACH_ERR_INVALID with a message and launches nothing.
+ *   ach_data_letterbox_batch  PIL Image.BICUBIC resize to (nw, nh) pasted at (dx, dy) on a (128, 128, 128) R x R canvas, then ((v / 255) - mean) / std through
+ *                       `lut`, 768 floats [channel][value] on the device.  Image table: 0 byte offset, 1 H, 2 W, 3 pitch, 4 nw, 5 nh, 6 dx, 7 dy, 8 horizontal
+ *                       bounds [nw][2], 9 horizontal coefficients [nw][ks], 10 ks, 11-13 the same for the vertical axis, 14 byte offset (a multiple of 4) into
+ *                       `mid`, 15 unused.  Bounds and coefficients as for ach_resample_pass_u8, over the whole axis.  dx, dy of either sign; the window may be
+ *                       larger than the canvas or outside it: the paste clips and only visible pixels are computed.  `arena`: 16-byte aligned, `arena_bytes` a
+ *                       multiple of 16.  `mid`: the 8-bit intermediate, per frame 3 * round_up(R, 4) bytes for every source row the visible rows need.
+ *                       out_kind 0 / 1 / 2: [B, 3, R, R] fp32 / bf16 / fp16 (one RNE rounding of the fp32 table value); 3: the bytes, [B, R, R, 3] (lut unused).
+ *                       Two launches; a row wider than 16379 needed source columns is ACH_ERR_UNSUPPORTED.
+ *   ach_data_labels_batch   PIL Image.NEAREST resize + paste on zeros + min(v, n) for both label maps of every frame in one launch: n = num_classes_seg for `png`,
+ *                       2 for `png_w`.  Label table: 0 nw, 1 nh, 2 dx, 3 dy, then per map (png at 4, png_w at 10): byte offset (negative: the frame has no such
+ *                       map, zeros are written), H, W, pitch, column index table [nw], row index table [nh] (source index per resized sample, -1: none).
+ *                       label_kind as ach_train_seg_loss: 0 int64, 2 uint8 outputs [B, R, R]. */
+int ach_data_letterbox_batch(const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const int32_t* tabs_host,
+                             const int32_t* tabs_dev, int64_t tabs_len, const float* lut, int32_t B, int32_t R, uint8_t* mid, int64_t mid_bytes, void* out,
+                             int32_t out_kind, void* stream);
+int ach_data_labels_batch(const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const int32_t* tabs_host,
+                          const int32_t* tabs_dev, int64_t tabs_len, int32_t B, int32_t R, int32_t num_classes_seg, void* png, void* png_w, int32_t label_kind,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
