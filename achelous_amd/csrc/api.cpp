@@ -17,6 +17,7 @@
 #include "k_loss.h"
 #include "k_metrics.h"
 #include "k_data.h"
+#include "k_serve.h"
 
 struct ach_handle {
     ach::EngineBase* eng = nullptr;
@@ -951,6 +952,70 @@ int ach_data_labels_batch(const uint8_t* arena, int64_t arena_bytes, const int64
         }
         ach::DataLabelParams lp{arena, reinterpret_cast<const long long*>(table_dev), tabs_dev, {png, png_w}, R, num_classes_seg, label_kind == 0 ? 1 : 0};
         ACH_LAUNCH(ach::data_labels_kernel, dim3(unsigned(ach::cdivl(long(R) * R, 256)), 2u, unsigned(B)), dim3(256), static_cast<hipStream_t>(stream), lp);
+    });
+}
+
+// ---- serving a ragged batch (k_serve.h): both class maps at every frame's own size and the overlay image in ONE launch behind the two softmax launches, and the
+// box correction with per-frame shapes.  The host copy of the frame table is checked against every arena before anything is launched.
+int ach_seg_overlay_frames(ach_handle* h, int32_t batch, int32_t channels, const void* se_seg, const void* lane_seg, float* prob_se, float* prob_line,
+                           const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const uint8_t* consts_host,
+                           const uint8_t* consts_dev, int32_t palette_se_len, int32_t palette_line_len, float blend_se, float blend_line, int32_t use_lut,
+                           uint8_t* out_semantic, int64_t semantic_bytes, uint8_t* out_waterline, int64_t waterline_bytes, uint8_t* out_overlay,
+                           int64_t overlay_bytes, void* stream) {
+    return guarded(h, [&] {
+        const bool want_se = out_semantic || out_overlay, want_line = out_waterline || out_overlay;
+        train_need(batch > 0 && batch <= 65535 && table_host && table_dev && (out_semantic || out_waterline || out_overlay), "ach_seg_overlay_frames: a batch, a frame table and an output");
+        train_need((!want_se || (se_seg && prob_se && channels >= 1 && channels <= 255)) && (!want_line || (lane_seg && prob_line)),
+                   "ach_seg_overlay_frames: every wanted output needs its head and probability workspace (1..255 classes)");
+        const int R = h->eng->cfg.resolution, C0 = want_se ? channels : 0, C1 = want_line ? 2 : 0;
+        if ((C0 + C1) * ach::SERVE_TW * 2 > ach::SERVE_LDS_FLOATS) throw ach::AchError{ACH_ERR_UNSUPPORTED, "ach_seg_overlay_frames: more than 30 semantic classes"};
+        auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
+        train_need(aligned(out_semantic) && aligned(out_waterline) && aligned(out_overlay) && semantic_bytes >= 0 && waterline_bytes >= 0 && overlay_bytes >= 0,
+                   "ach_seg_overlay_frames: output arenas are 16-byte aligned");
+        if (out_overlay) {
+            train_need(arena && consts_host && consts_dev && aligned(arena) && arena_bytes > 0 && arena_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(consts_dev) & 3u) == 0,
+                       "ach_seg_overlay_frames: the overlay needs the image arena (16-byte aligned, padded to 16 bytes) and the constants");
+            train_need(blend_se >= 0.f && blend_se <= 1.f && blend_line >= 0.f && blend_line <= 1.f, "ach_seg_overlay_frames: blend factors lie in [0, 1]");
+            train_need(palette_se_len >= 1 && palette_se_len <= 256 && palette_line_len >= 1 && palette_line_len <= 256, "ach_seg_overlay_frames: palettes hold 1..256 colours");
+            for (int c = 0; c < channels; ++c)
+                train_need(consts_host[ach::SERVE_REMAP_SE + c] < palette_se_len, "ach_seg_overlay_frames: the semantic palette is shorter than the remapped class range");
+            for (int c = 0; c < 2; ++c)
+                train_need(consts_host[ach::SERVE_REMAP_LINE + c] < palette_line_len, "ach_seg_overlay_frames: the water-line palette is shorter than the remapped class range");
+        }
+        const int rows = ach::serve_rows(C0 + C1);
+        long blocks = 0;
+        for (int b = 0; b < batch; ++b) {
+            const int64_t* f = table_host + long(b) * ach::SERVE_TABLE_COLS;
+            const int64_t H = f[1], W = f[2], y0 = f[4], x0 = f[5], nh = f[6], nw = f[7], mp = f[10];
+            train_need(H >= 1 && W >= 1 && H < (1L << 30) && W < (1L << 30), "ach_seg_overlay_frames: a frame's H and W are at least 1");
+            train_need(nh >= 1 && nw >= 1 && y0 >= 0 && x0 >= 0 && nh <= R - y0 && nw <= R - x0, "ach_seg_overlay_frames: a frame's window leaves the network map");
+            if (out_semantic || out_waterline) train_need(mp >= W && mp % 16 == 0 && mp < (1L << 32), "ach_seg_overlay_frames: the class maps' pitch is a multiple of 16, at least W");
+            if (out_semantic) train_need(f[8] >= 0 && f[8] % 16 == 0 && f[8] <= semantic_bytes && H * mp <= semantic_bytes - f[8], "ach_seg_overlay_frames: a frame's semantic map passes its arena");
+            if (out_waterline) train_need(f[9] >= 0 && f[9] % 16 == 0 && f[9] <= waterline_bytes && H * mp <= waterline_bytes - f[9], "ach_seg_overlay_frames: a frame's water-line map passes its arena");
+            if (out_overlay) {
+                const int64_t off = f[0], pitch = f[3], op = f[12];
+                train_need(pitch >= 3 * W && pitch < (1L << 32) && off >= 0 && off <= arena_bytes && (H - 1) * pitch + 3 * W <= arena_bytes - off,
+                           "ach_seg_overlay_frames: a frame's extent passes the image arena");
+                train_need(op >= 3 * W && op % 16 == 0 && op < (1L << 32) && f[11] >= 0 && f[11] % 16 == 0 && f[11] <= overlay_bytes && H * op <= overlay_bytes - f[11],
+                           "ach_seg_overlay_frames: a frame's overlay passes its arena");
+            }
+            blocks = std::max(blocks, ach::cdivl(W, ach::SERVE_TW) * ach::cdivl(nh, rows - 1));
+        }
+        train_need(blocks < (1L << 31), "ach_seg_overlay_frames: a frame is too large");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (want_se) h->eng->seg_softmax(batch, channels, se_seg, prob_se, s);
+        if (want_line) h->eng->seg_softmax(batch, 2, lane_seg, prob_line, s);
+        ach::ServeParams p{prob_se, prob_line, arena, reinterpret_cast<const long long*>(table_dev), consts_dev, out_semantic, out_waterline, out_overlay,
+                           R, C0, C1, rows, blend_se, blend_line, use_lut != 0};
+        ACH_LAUNCH(ach::seg_overlay_frames_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
+    });
+}
+int ach_correct_boxes_frames(ach_handle* h, int32_t batch, int32_t max_det, const float* rows, const int32_t* count, const int32_t* shapes_host,
+                             const int32_t* shapes_dev, int32_t letterbox, float* out_rows, void* stream) {
+    return guarded(h, [&] {
+        train_need(batch > 0 && max_det > 0 && rows && count && shapes_host && shapes_dev && out_rows, "ach_correct_boxes_frames");
+        for (int b = 0; b < batch; ++b) train_need(shapes_host[2 * b] >= 1 && shapes_host[2 * b + 1] >= 1, "ach_correct_boxes_frames: a frame's H and W are at least 1");
+        h->eng->correct_boxes_frames(batch, max_det, rows, count, shapes_dev, letterbox, out_rows, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -307,6 +307,11 @@ void EngineBase::correct_boxes(int B, int max_det, const float* rows, const int*
     ACH_LAUNCH(correct_boxes_kernel, dim3(unsigned(cdivl(long(B) * max_det, 256))), dim3(256), s, p);
 }
 
+void EngineBase::correct_boxes_frames(int B, int max_det, const float* rows, const int* count, const int* shapes_dev, int letterbox, float* out, hipStream_t s) {
+    BoxCorrectParams p{rows, count, out, B, max_det, double(cfg.resolution), double(cfg.resolution), 0.0, 0.0, letterbox};
+    ACH_LAUNCH(correct_boxes_frames_kernel, dim3(unsigned(cdivl(long(B) * max_det, 256))), dim3(256), s, p, shapes_dev);
+}
+
 std::vector<long> EngineBase::tap_shape(const std::string& name) const {
     auto it = taps.find(name);
     if (it == taps.end()) throw AchError{ACH_ERR_INVALID, "unknown tap: " + name};

@@ -206,6 +206,10 @@ public:
     virtual void seg_argmax(int B, int C, const void* seg, unsigned char* out, hipStream_t s) = 0;
     virtual void seg_resize_argmax(int B, int C, const void* seg, int out_h, int out_w, float* prob_ws, unsigned char* out, hipStream_t s) = 0;
     void correct_boxes(int B, int max_det, const float* rows, const int* count, int img_h, int img_w, int letterbox, float* out, hipStream_t s);
+    // the ragged-batch forms (k_serve.h, k_prepost.h): the softmax of one head into an fp32 workspace [B, C, R, R] (what seg_resize_argmax runs first), and the box
+    // correction with every frame's (H, W) read from an int32 [B, 2] table on the device
+    virtual void seg_softmax(int B, int C, const void* seg, float* prob_ws, hipStream_t s) = 0;
+    void correct_boxes_frames(int B, int max_det, const float* rows, const int* count, const int* shapes_dev, int letterbox, float* out, hipStream_t s);
     float* prepost_scratch = nullptr; size_t prepost_scratch_bytes = 0;
     // micro-benchmark hook: time the MFMA GEMM kernel alone on scratch buffers (ms per launch)
     virtual float bench_gemm(int M, int K, int N, int act, int ln, int residual, int P, int iters, hipStream_t s) = 0;

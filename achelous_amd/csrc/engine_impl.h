@@ -2444,12 +2444,15 @@ public:
     }
 
     // achelous.py:283-318: softmax -> crop the letterbox bars -> INTER_LINEAR resize to the original size -> argmax (k_prepost.h)
-    void seg_resize_argmax(int B, int C, const void* seg, int out_h, int out_w, float* prob_ws, unsigned char* out, hipStream_t s) override {
-        const int R = cfg.resolution;
-        const long HW = long(R) * R;
+    void seg_softmax(int B, int C, const void* seg, float* prob_ws, hipStream_t s) override {
+        const long HW = long(cfg.resolution) * cfg.resolution;
         SegSoftmaxParams sp{seg, prob_ws, B, C, HW};
         if (io_alt()) ACH_LAUNCH(seg_softmax_kernel<IOB>, dim3(unsigned(cdivl(HW * B, 256))), dim3(256), s, sp);
         else ACH_LAUNCH(seg_softmax_kernel<T>, dim3(unsigned(cdivl(HW * B, 256))), dim3(256), s, sp);
+    }
+    void seg_resize_argmax(int B, int C, const void* seg, int out_h, int out_w, float* prob_ws, unsigned char* out, hipStream_t s) override {
+        const int R = cfg.resolution;
+        seg_softmax(B, C, seg, prob_ws, s);
         // utils_seg/utils.py:19-31 (resize_image): scale = min(w / iw, h / ih), nw = int(iw * scale), nh = int(ih * scale), centred
         const double scale = std::min(double(R) / double(out_w), double(R) / double(out_h));
         const int nw = std::max(1, int(double(out_w) * scale)), nh = std::max(1, int(double(out_h) * scale));

@@ -145,9 +145,7 @@ static __global__ __launch_bounds__(256) void seg_resize_argmax_kernel(const Seg
 // out  [B, max_det, 7] = y1, x1, y2, x2 in pixels of the ORIGINAL image, other columns copied.  The reference does this in numpy
 // with float64 intermediates (a float32 array combined with float64 shape arrays) and stores float32: same here, in double.
 struct BoxCorrectParams { const float* rows; const int* count; float* out; int B, max_det; double in_h, in_w, img_h, img_w; int letterbox; };
-static __global__ __launch_bounds__(256) void correct_boxes_kernel(const BoxCorrectParams p) {
-    const long idx = long(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (idx >= long(p.B) * p.max_det) return;
+__device__ __forceinline__ void correct_box_row(const BoxCorrectParams& p, long idx) {
     const int b = int(idx / p.max_det), k = int(idx % p.max_det);
     const float* r = p.rows + idx * 7;
     float* o = p.out + idx * 7;
@@ -171,6 +169,19 @@ static __global__ __launch_bounds__(256) void correct_boxes_kernel(const BoxCorr
     o[0] = float(y_lo * p.img_h); o[1] = float(x_lo * p.img_w);                        // `boxes *= image_shape`: computed in float64, stored float32
     o[2] = float(y_hi * p.img_h); o[3] = float(x_hi * p.img_w);
     o[4] = r[4]; o[5] = r[5]; o[6] = r[6];
+}
+static __global__ __launch_bounds__(256) void correct_boxes_kernel(const BoxCorrectParams p) {
+    const long idx = long(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (idx >= long(p.B) * p.max_det) return;
+    correct_box_row(p, idx);
+}
+// the same for a ragged batch: every frame's own (H, W) from an int32 [B, 2] table on the device (`img_h` / `img_w` of the parameters are not read)
+static __global__ __launch_bounds__(256) void correct_boxes_frames_kernel(BoxCorrectParams p, const int* __restrict__ shapes) {
+    const long idx = long(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (idx >= long(p.B) * p.max_det) return;
+    const long b = idx / p.max_det;
+    p.img_h = double(shapes[2 * b]); p.img_w = double(shapes[2 * b + 1]);
+    correct_box_row(p, idx);
 }
 
 // One pass of Pillow's ImagingResample for 8-bit pixels (the reference letterboxes with PIL: utils/utils.py:20-33, Image.BICUBIC): every output

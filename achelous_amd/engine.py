@@ -41,7 +41,7 @@ class NativeLibrary:
                'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
                'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
                'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss',
-               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch')
+               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch', 'ach_seg_overlay_frames', 'ach_correct_boxes_frames')
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -147,7 +147,9 @@ class NativeLibrary:
                            ('ach_eval_confusion', [vp, i32, i32, vp, i32, i32, i32, i64, vp, vp]),
                            ('ach_eval_match', [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
                            ('ach_data_letterbox_batch', [vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, i64, vp, i32, vp]),
-                           ('ach_data_labels_batch', [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, vp])):
+                           ('ach_data_labels_batch', [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]),
+                           ('ach_seg_overlay_frames', [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, i64, vp, i64, vp, i64, vp]),
+                           ('ach_correct_boxes_frames', [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp])):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = ctypes.c_int
         L.ach_record_words.argtypes = [i32, i32]
@@ -382,6 +384,22 @@ class NativeEngine:
     def correct_boxes(self, batch, max_det, rows, count, image_h, image_w, letterbox, out, stream=0):
         self._check(self.L.ach_correct_boxes(self.h, int(batch), int(max_det), _ptr(rows), _ptr(count), int(image_h), int(image_w),
                                              int(bool(letterbox)), _ptr(out), ctypes.c_void_p(stream)))
+
+    def seg_overlay_frames(self, batch, channels, se, lane, prob_se, prob_line, arena, arena_bytes, table_host, table_dev, consts_host, consts_dev,
+                           palette_se_len, palette_line_len, blend_se, blend_line, use_lut, out_semantic, semantic_bytes, out_waterline, waterline_bytes,
+                           out_overlay, overlay_bytes, stream=0):
+        """the ragged batch's class maps and overlay in one launch behind the softmax launches (include/achelous.h); the table / constants arguments are raw
+        addresses (host copy, device copy), every other pointer a tensor or None"""
+        vp = ctypes.c_void_p
+        self._check(self.L.ach_seg_overlay_frames(self.h, int(batch), int(channels), _ptr(se), _ptr(lane), _ptr(prob_se), _ptr(prob_line), _ptr(arena), int(arena_bytes),
+                                                  vp(table_host), vp(table_dev), vp(consts_host), vp(consts_dev), int(palette_se_len), int(palette_line_len),
+                                                  float(blend_se), float(blend_line), int(bool(use_lut)), _ptr(out_semantic), int(semantic_bytes),
+                                                  _ptr(out_waterline), int(waterline_bytes), _ptr(out_overlay), int(overlay_bytes), vp(stream)))
+
+    def correct_boxes_frames(self, batch, max_det, rows, count, shapes_host, shapes_dev, letterbox, out, stream=0):
+        """`correct_boxes` with a (H, W) per frame: int32 [batch, 2], host copy and device copy (raw addresses)"""
+        self._check(self.L.ach_correct_boxes_frames(self.h, int(batch), int(max_det), _ptr(rows), _ptr(count), ctypes.c_void_p(shapes_host), ctypes.c_void_p(shapes_dev),
+                                                    int(bool(letterbox)), _ptr(out), ctypes.c_void_p(stream)))
 
     # ---------------------------------------------------------------------------------------------------
     def tap_names(self):

@@ -5,10 +5,15 @@
     preprocess_input(images[B,R,R,3] uint8)          utils/utils.py:44-48   -> [B,3,R,R] dtype   (letterboxing stays on the host)
     seg_class_map(seg[B,C,R,R])                      achelous.py:283-296    -> uint8 [B,R,R]     (network resolution)
     seg_class_map_original(seg[B,C,R,R], (h, w))     achelous.py:283-318    -> uint8 [B,h,w]     softmax -> crop bars -> INTER_LINEAR -> argmax
+    seg_maps_frames(se, lane, shapes, arena)         achelous.py:283-345    -> per-frame views   both class maps + the overlay image, ragged batch, one launch
+    correct_boxes_frames(rows, cnt, (R, R), shapes)  utils_bbox.py:5-30     -> [B,max_det,7]     every frame's own (H, W)
+    detect_frames(net, frames, radar, points)        achelous.py:190-345    camera bytes of B frames of different sizes -> boxes, class maps, overlays
 HIP kernels through the C ABI; no CPU fallback.
 """
+import contextlib
 import math
 
+import numpy as np
 import torch
 
 from . import engine as _eng
@@ -192,3 +197,216 @@ def detect_frame(net, image_u8, radar_map, points, conf_thres=0.5, nms_thres=0.4
     boxes = correct_boxes_device(rows, cnt, (R, R), (H, W), letterbox_image)
     sem, wl = seg_class_map_original(se, (H, W)), seg_class_map_original(lane, (H, W))
     return {'boxes': boxes[0, :int(cnt[0])], 'semantic': sem[0], 'waterline': wl[0], 'point_class': pc[0].float().argmax(-1)}
+
+
+# ------------------------------------------------------------------------------------------------- a ragged batch: class maps, overlays, boxes (csrc/k_serve.h)
+# the reference's two colour lists for up to 21 classes (achelous.py:135-142; the water-line list is the same list reversed)
+PALETTE_SEG = ((0, 0, 0), (128, 0, 0), (0, 128, 0), (128, 128, 0), (0, 0, 128), (128, 0, 128), (0, 128, 128), (128, 128, 128), (64, 0, 0), (192, 0, 0), (64, 128, 0),
+               (192, 128, 0), (64, 0, 128), (192, 0, 128), (64, 128, 128), (192, 128, 128), (0, 64, 0), (128, 64, 0), (0, 192, 0), (128, 192, 0), (0, 64, 128),
+               (128, 64, 12))
+PALETTE_LINE = tuple(reversed(PALETTE_SEG))
+SERVE_TABLE_COLS = 16        # k_serve.h
+_SERVE_OUTPUTS = ('semantic', 'waterline', 'overlay')
+_frame_handles = {}
+
+
+def _frames_handle(t, R, dtype):
+    """the engine handle whose softmax serves tensors like `t` (tests: the emulation library through `_pass_lib.test_library`)"""
+    lib = getattr(_pass_lib, 'test_library', None)
+    if lib is None:
+        _need_gpu(t, 'a ragged-batch call')
+        return _handle(1, R, dtype)
+    code = {torch.float32: _eng.DTYPE_F32, torch.bfloat16: _eng.DTYPE_BF16, torch.float16: _eng.DTYPE_F16}[dtype]
+    if (R, code) not in _frame_handles:
+        _frame_handles[(R, code)] = _eng.NativeEngine(lib, num_det=1, num_seg=1, phi='S0', backbone='en', resolution=R, pc_channels=3, pc_classes=1, num_points=16,
+                                                      nano_head=True, spp=True, dtype=code)
+    return _frame_handles[(R, code)]
+
+
+def _stream_of(t):
+    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+
+
+def _frame_shapes(shapes, B):
+    out = [(int(s[0]), int(s[1])) for s in shapes]
+    if len(out) != B:
+        raise ValueError(f"shapes: one (H, W) per frame expected, got {len(out)} for a batch of {B}")
+    if any(h < 1 or w < 1 for h, w in out):
+        raise ValueError("shapes: H and W are at least 1")
+    return out
+
+
+def letterbox_window(h, w, R):
+    """(y0, x0, nh, nw): the part of the R x R network map the letterbox of an (h, w) frame fills (utils_seg/utils.py:19-31, as `seg_class_map_original` crops it)"""
+    scale = min(R / w, R / h)
+    nw, nh = max(1, int(w * scale)), max(1, int(h * scale))
+    return (R - nh) // 2, (R - nw) // 2, nh, nw
+
+
+def brightness_table(factor):
+    """ImageEnhance.Brightness(image).enhance(factor) per byte: Image.blend(black, image, factor) = factor * v in float32, <= 0 -> 0, >= 255 -> 255, else truncated"""
+    t = np.float32(factor) * np.arange(256, dtype=np.float32)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, np.trunc(t))).astype(np.uint8)
+
+
+def frames_layout(shapes):
+    """Where `seg_maps_frames` puts every frame in its output arenas: (map offsets, map pitches, map bytes, overlay offsets, overlay pitches, overlay bytes).
+    Pitches are rounded up to 16 bytes, so frame starts are 16-byte aligned."""
+    moff, mp, ooff, op, mt, ot = [], [], [], [], 0, 0
+    for h, w in shapes:
+        mp.append((w + 15) // 16 * 16)
+        op.append((3 * w + 15) // 16 * 16)
+        moff.append(mt)
+        ooff.append(ot)
+        mt += h * mp[-1]
+        ot += h * op[-1]
+    return moff, mp, mt, ooff, op, ot
+
+
+def _seg_maps_plan(se, lane, shapes, arena=None, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3,
+                   want=_SERVE_OUTPUTS, windows=None, workspaces=None, out=None, meta_name='serve'):
+    """everything `seg_maps_frames` does on the host (checks, frame table, constants, one upload, arenas); returns the launch as a callable.  A caller that keeps the
+    callable and launches it again later passes a `meta_name` of its own: the pinned copy of the tables, which every launch re-checks, is reused per name"""
+    from . import data as _data
+    s, ln = se.contiguous(), lane.contiguous()
+    B, C, R, _ = s.shape
+    if ln.shape != (B, 2, R, R) or ln.dtype != s.dtype or s.shape[3] != R:
+        raise ValueError("seg_maps_frames: se [B, C, R, R] and lane [B, 2, R, R] of one dtype expected")
+    shapes = _frame_shapes(shapes, B)
+    want = tuple(w for w in _SERVE_OUTPUTS if w in want and (w != 'overlay' or arena is not None))
+    if not want or any(w not in _SERVE_OUTPUTS for w in want):
+        raise ValueError(f"seg_maps_frames: `want` names some of {_SERVE_OUTPUTS} (the overlay needs `arena`)")
+    wins = [letterbox_window(h, w, R) for h, w in shapes] if windows is None else [tuple(int(v) for v in w) for w in windows]
+    if len(wins) != B:
+        raise ValueError("seg_maps_frames: one window per frame")
+    moff, mp, mbytes, ooff, op, obytes = frames_layout(shapes)
+    table = np.zeros((B, SERVE_TABLE_COLS), np.int64)
+    for b, ((h, w), win) in enumerate(zip(shapes, wins)):
+        table[b, 1:3] = (h, w)
+        table[b, 4:8] = win
+        table[b, 8:13] = (moff[b], moff[b], mp[b], ooff[b], op[b])
+    meta = _data._Meta(s.device, meta_name)
+    consts = None
+    n_se = n_line = 0
+    if 'overlay' in want:
+        if len(arena.frames) != B or any(f is None or (f[1], f[2]) != sh for f, sh in zip(arena.frames, shapes)):
+            raise ValueError("seg_maps_frames: `arena` holds one image per frame, of the sizes in `shapes`")
+        for b, f in enumerate(arena.frames):
+            table[b, 0], table[b, 3] = f[0], f[3]
+        pal = [np.asarray(p, dtype=np.uint8).reshape(-1, 3) for p in (palette_se, palette_line)]
+        if any(len(p) < 1 or len(p) > 256 for p in pal):
+            raise ValueError("seg_maps_frames: a palette holds 1..256 colours")
+        n_se, n_line = len(pal[0]), len(pal[1])
+        c = np.zeros(2304, np.uint8)
+        c[0:3 * n_se], c[768:768 + 3 * n_line] = pal[0].reshape(-1), pal[1].reshape(-1)
+        ident = np.arange(256, dtype=np.uint8)
+        c[1536:1792] = ident if keep_classes is None else np.where(np.isin(ident, np.asarray(keep_classes, dtype=np.int64)), ident, 0)
+        c[1792:2048] = ident
+        if brightness is not None:
+            c[2048:2304] = brightness_table(brightness)
+        consts = meta.add(c)
+    tref = meta.add(table)
+    meta.commit()
+    dev = s.device
+    sizes = {'semantic': mbytes, 'waterline': mbytes, 'overlay': obytes}
+    arenas = {}
+    for name in want:
+        a = (out or {}).get(name)
+        if a is None:
+            a = torch.empty(max(sizes[name], 16), dtype=torch.uint8, device=dev)
+        elif a.dtype != torch.uint8 or a.dim() != 1 or not a.is_contiguous() or a.device != dev or a.numel() < sizes[name]:
+            raise ValueError(f"seg_maps_frames: out[{name!r}] is a contiguous 1-D uint8 tensor of at least {sizes[name]} bytes on the inputs' device")
+        arenas[name] = a
+    if workspaces is None:
+        workspaces = (torch.empty(B * C * R * R, dtype=torch.float32, device=dev), torch.empty(B * 2 * R * R, dtype=torch.float32, device=dev))
+    ws_se, ws_line = workspaces
+    if ws_se.dtype != torch.float32 or ws_line.dtype != torch.float32 or ws_se.numel() < B * C * R * R or ws_line.numel() < B * 2 * R * R or ws_se.device != dev or ws_line.device != dev:
+        raise ValueError("seg_maps_frames: workspaces are fp32 tensors of B * C * R * R and B * 2 * R * R elements on the inputs' device")
+    h = _frames_handle(s, R, s.dtype)
+    addr = lambda ref: (meta.host_ptr(ref).value, meta.dev_ptr(ref).value) if ref is not None else (None, None)
+    nbytes = lambda name: arenas[name].numel() if name in arenas else 0
+    ctx = torch.cuda.device(dev) if s.is_cuda else contextlib.nullcontext()
+
+    def run():
+        with ctx:
+            h.seg_overlay_frames(B, C, s, ln, ws_se, ws_line, arena.data if 'overlay' in want else None, arena.data.numel() if 'overlay' in want else 0,
+                                 *addr(tref), *addr(consts), n_se, n_line, blend[0], blend[1], brightness is not None, arenas.get('semantic'), nbytes('semantic'),
+                                 arenas.get('waterline'), nbytes('waterline'), arenas.get('overlay'), nbytes('overlay'), _stream_of(s))
+        res = {'arenas': arenas}
+        for name in want:
+            a = arenas[name]
+            if name == 'overlay':
+                res[name] = [torch.as_strided(a, (hh, ww, 3), (op[b], 3, 1), ooff[b]) for b, (hh, ww) in enumerate(shapes)]
+            else:
+                res[name] = [torch.as_strided(a, (hh, ww), (mp[b], 1), moff[b]) for b, (hh, ww) in enumerate(shapes)]
+        return res
+    return run
+
+
+
+def seg_maps_frames(se, lane, shapes, arena=None, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3,
+                    want=_SERVE_OUTPUTS, windows=None, workspaces=None, out=None):
+    """What the reference's detect_image computes from the two segmentation outputs (achelous.py:283-345), for B frames of DIFFERENT sizes in one launch behind
+    the two softmax launches: `se` [B, C, R, R], `lane` [B, 2, R, R], `shapes` one (H, W) per frame.
+
+    semantic / waterline: the class map at the frame's own size, exactly `seg_class_map_original` per frame (the arg-max itself; `keep_classes` does not touch it).
+    overlay: [H, W, 3] uint8 = Brightness(blend(blend(image, palette_se[class'], blend[0]), palette_line[line class], blend[1])).enhance(brightness), PIL's
+    arithmetic byte for byte; class' = class if class in `keep_classes` else 0 (achelous.py:297 is keep_classes=(0, 8); None keeps all); brightness None: no
+    enhancement.  Needs `arena`, the `data.Arena` the frames were uploaded in (`data.pack_arena`); with arena=None only the class maps are produced.
+
+    Returns a dict of lists of per-frame VIEWS into one packed arena per output (row pitch rounded up to 16 bytes: the views are strided, nothing is copied), and
+    under 'arenas' the arenas themselves.  `windows`: per frame (y0, x0, nh, nw) of the network map instead of the letterbox's window.  `workspaces`: the two fp32
+    probability buffers (B * C * R * R and B * 2 * R * R) to use; `out`: dict name -> 1-D uint8 tensor to use as that output's arena (`frames_layout`).
+    No host read, no synchronisation."""
+    return _seg_maps_plan(se, lane, shapes, arena, palette_se, palette_line, keep_classes, blend, brightness, want, windows, workspaces, out)()
+
+
+def correct_boxes_frames(rows, cnt, input_shape, shapes, letterbox_image):
+    """`postprocess.correct_boxes_device` for a ragged batch: kept rows [B, max_det, 7] -> (y1, x1, y2, x2) in pixels of EACH frame's own image, `shapes` one (H, W)
+    per frame; rows past cnt[b] are zero.  One launch; the shapes travel in one non-blocking copy."""
+    from . import data as _data
+    R = int(input_shape[0])
+    if int(input_shape[1]) != R:
+        raise ValueError("square network input expected")
+    rows = rows.contiguous()
+    B, max_det, _ = rows.shape
+    shapes = _frame_shapes(shapes, B)
+    meta = _data._Meta(rows.device, 'serve_boxes')
+    ref = meta.add(np.asarray(shapes, dtype=np.int32))
+    meta.commit()
+    out = torch.empty_like(rows)
+    h = _frames_handle(rows, R, torch.float32)
+    ctx = torch.cuda.device(rows.device) if rows.is_cuda else contextlib.nullcontext()
+    with ctx:
+        h.correct_boxes_frames(B, max_det, rows, cnt.contiguous(), meta.host_ptr(ref).value, meta.dev_ptr(ref).value, letterbox_image, out, _stream_of(rows))
+    return out
+
+
+def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4, letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True,
+                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3):
+    """`detect_frame` for B frames of DIFFERENT sizes: the arithmetic of the reference's detect_image (achelous.py:190-345) without its file I/O and box drawing.
+
+    frames: a list of CPU uint8 [H_i, W_i, 3] arrays / tensors, or a `data.Arena` already on the device; radar_maps [B, 3, R, R] float and points
+    [B, N, pc_channels] float on the GPU.  One upload (`data.pack_arena`), the letterbox of all frames in two launches (`data.letterbox_batch`; with
+    letterbox_image=False every frame is stretched over the whole input), the batched radar / point preparation, ONE `forward_detect`, one box-correction launch
+    and one launch for both class maps and the overlay of every frame.  The launch count does not depend on B and nothing is read back or synchronised, so the
+    boxes are NOT cut to their count here: the caller slices `boxes[b, :count[b]]` when it reads `count`.
+
+    Returns dict(boxes [B, max_det, 7] = (y1, x1, y2, x2 in the frame's own pixels, obj, class conf, class id), rows past count[b] zero; count [B] int32;
+    semantic, waterline: lists of [H_i, W_i] uint8 views; overlay: list of [H_i, W_i, 3] uint8 views (overlay=True; `seg_maps_frames`); point_class [B, N] int64)."""
+    from . import data as _data
+    R = net.resolution
+    arena = _data._as_arena(frames, 3, radar_maps.device, 'images')
+    B = len(arena.frames)
+    shapes = [(f[1], f[2]) for f in arena.frames]
+    x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
+    xr = preprocess_input_radar(radar_maps, dtype)
+    xp = normalize_points(points, dtype)
+    (det, se, lane, pc), (rows, idx, cnt) = net.forward_detect(x, xr, xp, conf_thres, nms_thres, max_det)
+    boxes = correct_boxes_frames(rows, cnt, (R, R), shapes, letterbox_image)
+    maps = seg_maps_frames(se, lane, shapes, arena if overlay else None, palette_se, palette_line, keep_classes, blend, brightness,
+                           windows=None if letterbox_image else [(0, 0, R, R)] * B)
+    res = {'boxes': boxes, 'count': cnt, 'semantic': maps['semantic'], 'waterline': maps['waterline'], 'point_class': pc.float().argmax(-1)}
+    if overlay:
+        res['overlay'] = maps['overlay']
+    return res

@@ -218,6 +218,33 @@ int ach_seg_resize_argmax(ach_handle* h, int32_t batch, int32_t channels, const 
 int ach_correct_boxes(ach_handle* h, int32_t batch, int32_t max_det, const float* rows, const int32_t* count, int32_t image_h, int32_t image_w,
                       int32_t letterbox, float* out_rows, void* stream);
 
+/* The same two steps for a RAGGED batch — frames of different sizes in one call, a fixed number of launches whatever the batch (achelous_amd/csrc/k_serve.h):
+ *   ach_seg_overlay_frames  <- achelous.py:283-345  both heads' class maps at every frame's own size (the arithmetic of ach_seg_resize_argmax, operation for
+ *                       operation) and the overlay image detect_image draws: palette lookup, Image.blend twice, ImageEnhance.Brightness.  Two softmax launches
+ *                       and ONE launch for all frames, both heads and all outputs.  se_seg [B, channels, R, R], lane_seg [B, 2, R, R] (config dtype);
+ *                       prob_se / prob_line: batch * channels * R * R and batch * 2 * R * R floats.  Each output is optional (null: skipped, and a head no
+ *                       wanted output needs is not read): out_semantic / out_waterline uint8 class maps (the arg-max itself, not remapped), out_overlay uint8
+ *                       HWC.  The original images sit in `arena`, a packed uint8 buffer (HWC, 16-byte aligned, `arena_bytes` a multiple of 16; needed for the
+ *                       overlay only).  Every output is a packed arena of its own: 16-byte aligned, frame starts and row pitches multiples of 16.
+ *                       Frame table int64 [batch][16], host copy and device copy: 0 byte offset of the image in `arena`, 1 H, 2 W, 3 image pitch (>= 3 W),
+ *                       4 y0, 5 x0, 6 nh, 7 nw (the window of the R x R network map that is stretched over the frame: the letterbox's, utils_seg/utils.py:19-31,
+ *                       or any other inside the map), 8 byte offset of the semantic map in out_semantic, 9 of the water-line map in out_waterline, 10 pitch of
+ *                       both maps (>= W), 11 byte offset of the overlay in out_overlay, 12 overlay pitch (>= 3 W), 13-15 unused.
+ *                       Constants, 2304 bytes, host copy and device copy (overlay only): semantic palette [256][3], water-line palette [256][3], semantic class
+ *                       remap [256], water-line class remap [256], brightness table [256] (read when use_lut != 0):
+ *                       overlay = table[blend(blend(image, palette_se[remap_se[class]], blend_se), palette_line[remap_line[line class]], blend_line)],
+ *                       blend(a, b, t) = (uint8)(a + t * (b - a)) in float32 as PIL's Image.blend, 0 <= t <= 1.  palette_*_len: colours the caller filled.
+ *                       The host copies are checked before anything is launched: an extent past an arena, a bad pitch or alignment, H or W < 1, a window
+ *                       outside the map, a remapped class past its palette -> ACH_ERR_INVALID, no launch.  More than 30 semantic classes: ACH_ERR_UNSUPPORTED.
+ *   ach_correct_boxes_frames  ach_correct_boxes with every frame's (image_h, image_w) read from an int32 [batch][2] table (host copy checked, device copy read). */
+int ach_seg_overlay_frames(ach_handle* h, int32_t batch, int32_t channels, const void* se_seg, const void* lane_seg, float* prob_se, float* prob_line,
+                           const uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, const uint8_t* consts_host,
+                           const uint8_t* consts_dev, int32_t palette_se_len, int32_t palette_line_len, float blend_se, float blend_line, int32_t use_lut,
+                           uint8_t* out_semantic, int64_t semantic_bytes, uint8_t* out_waterline, int64_t waterline_bytes, uint8_t* out_overlay,
+                           int64_t overlay_bytes, void* stream);
+int ach_correct_boxes_frames(ach_handle* h, int32_t batch, int32_t max_det, const float* rows, const int32_t* count, const int32_t* shapes_host,
+                             const int32_t* shapes_dev, int32_t letterbox, float* out_rows, void* stream);
+
 /* Range guard of the fp16-storage engine (ACH_DTYPE_F16).  The reference runs fp32 or, under autocast, fp16 WITH torch's GradScaler / inf checks
  * (utils/utils_fit.py:120-166); bf16 callers (BASELINE configs[1]) are served by fp16 storage inside, which overflows at 65504 where bf16 does not.
  * Every kernel of that engine therefore runs with MODE.FP16_OVFL (overflowing conversions clamp to +-65504, never infinity), and this entry counts the
