@@ -24,7 +24,7 @@ import torch
 
 from . import prepost as _pp
 from .losses import pack_labels
-from .train_ops import _lib, _p, _stream
+from ._native import lib as _lib, check as _check, ptr as _p, stream as _stream, stateless_handle
 
 TABLE_COLS = 16          # DATA_TABLE_COLS of k_data.h
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -34,11 +34,6 @@ _ERRORS = {-1: ValueError, -2: NotImplementedError}
 
 Batch = collections.namedtuple('Batch', 'images radar points boxes counts png png_w pc_labels')
 Arena = collections.namedtuple('Arena', 'data frames')          # data: 1-D uint8 tensor on the device; frames: per frame (byte offset, H, W, pitch) or None
-
-
-def _check(lib, rc):
-    if rc != 0:
-        raise _ERRORS.get(rc, RuntimeError)((lib.lib.ach_last_error(None) or b'data kernel failed').decode())
 
 
 # ------------------------------------------------------------------------------------------------------------------ host rules
@@ -272,7 +267,7 @@ def _launch_images(meta, arena, ref, mid_bytes, lut_ref, R, dtype):
     mid = torch.empty(mid_bytes, dtype=torch.uint8, device=data.device)
     out = torch.empty((B, R, R, 3) if dtype == torch.uint8 else (B, 3, R, R), dtype=dtype, device=data.device)
     _check(lib, lib.lib.ach_data_letterbox_batch(_p(data), data.numel(), meta.host_ptr(ref), meta.dev_ptr(ref), meta.host_ptr(meta.tabs_ref), meta.dev_ptr(meta.tabs_ref),
-                                                 meta.tab_len, meta.dev_ptr(lut_ref), B, R, _p(mid), mid_bytes, _p(out), _OUT_KIND[dtype], _stream(data)))
+                                                 meta.tab_len, meta.dev_ptr(lut_ref), B, R, _p(mid), mid_bytes, _p(out), _OUT_KIND[dtype], _stream(data)), _ERRORS, 'data kernel')
     return out
 
 
@@ -296,7 +291,7 @@ def _launch_labels(meta, data, ref, B, R, num_classes_seg, label_dtype):
     png = torch.empty(B, R, R, dtype=label_dtype, device=data.device)
     png_w = torch.empty(B, R, R, dtype=label_dtype, device=data.device)
     _check(lib, lib.lib.ach_data_labels_batch(_p(data), data.numel(), meta.host_ptr(ref), meta.dev_ptr(ref), meta.host_ptr(meta.tabs_ref), meta.dev_ptr(meta.tabs_ref),
-                                              meta.tab_len, B, R, int(num_classes_seg), _p(png), _p(png_w), _LABEL_KIND[label_dtype], _stream(data)))
+                                              meta.tab_len, B, R, int(num_classes_seg), _p(png), _p(png_w), _LABEL_KIND[label_dtype], _stream(data)), _ERRORS, 'data kernel')
     return png, png_w
 
 
@@ -345,12 +340,9 @@ def _normalize_points(points, dtype):
     lib = getattr(_lib, 'test_library', None)
     if lib is None:
         return _pp.normalize_points(points, dtype)
-    from . import engine as _eng                         # tests: the same kernel under the emulation library
-    code = {torch.float32: _eng.DTYPE_F32, torch.bfloat16: _eng.DTYPE_BF16, torch.float16: _eng.DTYPE_F16}[dtype]
-    h = _eng.NativeEngine(lib, num_det=1, num_seg=1, phi='S0', backbone='en', resolution=32, pc_channels=3, pc_classes=1, num_points=16, nano_head=True, spp=True, dtype=code)
-    B, N, D = points.shape
+    B, N, D = points.shape                               # tests: the same kernel under the emulation library
     out = torch.empty(B, D, N, dtype=dtype, device=points.device)
-    h.normalize_points(B, N, D, points.contiguous(), out)
+    stateless_handle(1, 32, dtype, lib).normalize_points(B, N, D, points.contiguous(), out)
     return out
 
 

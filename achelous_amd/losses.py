@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .train_ops import _lib, _check, _p, _stream
+from ._native import lib as _lib, check as _check, ptr as _p, stream as _stream, f32c as _f32c
 
 MAX_BOXES = 128          # boxes per image (YL_MAXG of k_loss.h)
 _MAX_ANCHORS = 5376      # YL_MAXA
@@ -38,12 +38,6 @@ def _amp_backward(fn):
         return torch.amp.custom_bwd(fn, device_type='cuda')
     except (AttributeError, TypeError):
         return torch.cuda.amp.custom_bwd(fn)
-
-
-def _f32c(t, what):
-    if t.dtype != torch.float32:
-        raise TypeError(f"{what}: the loss kernels are float32 (got {t.dtype}); run under torch.autocast or cast")
-    return t.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------------ detection

@@ -16,7 +16,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .train_ops import _lib, _check, _p, _stream
+from ._native import lib as _lib, check as _check, ptr as _p, stream as _stream
 
 MAX_CLASSES = 16         # CONF_MAXN of k_metrics.h
 MAX_DET = 1024           # MATCH_MAXD

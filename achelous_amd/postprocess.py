@@ -9,22 +9,7 @@ All of it runs as HIP kernels through the C ABI (ach_decode / ach_nms / ach_corr
 """
 import torch
 
-from . import engine as _eng
-
-_handles = {}
-
-
-def _handle(num_det, resolution, dtype):
-    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        # the kernels exist for fp32, bf16 and fp16 tensors only; any other element size would be read / written with the wrong stride
-        raise TypeError(f"achelous_amd kernels take float32, bfloat16 or float16 tensors, got {dtype}")
-    code = {torch.bfloat16: _eng.DTYPE_BF16, torch.float16: _eng.DTYPE_F16, torch.float32: _eng.DTYPE_F32}[dtype]
-    key = (torch.cuda.current_device(), num_det, resolution, code)
-    if key not in _handles:
-        _handles[key] = _eng.NativeEngine(_eng.hip_library(), num_det=num_det, num_seg=1, phi='S0', backbone='en',
-                                          resolution=resolution, pc_channels=3, pc_classes=1, num_points=16, nano_head=True,
-                                          spp=True, dtype=code)
-    return _handles[key]
+from ._native import stateless_handle as _handle          # _handle(num_det, resolution, dtype): the HIP library's handle on the current device
 
 
 def decode_outputs(outputs, input_shape, local_rank=None):

@@ -16,17 +16,15 @@ import math
 import numpy as np
 import torch
 
-from . import engine as _eng
+from ._native import lib as _pass_lib, check as _check, stream as _stream, stateless_handle
 from .postprocess import _handle
 
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} needs a GPU tensor (HIP kernel; no CPU path)")
+# `_pass_lib(t)` is `_native.lib` (tests set `_pass_lib.test_library`): it raises RuntimeError for a CPU tensor.  The single-shape entries below always run on the
+# HIP library through `_handle`; they call it for that check alone (with a test library set a CPU tensor gets as far as `torch.cuda.device`, which refuses it).
 
 
 def preprocess_input_radar(radar, dtype=torch.float32):
-    _need_gpu(radar, 'preprocess_input_radar')
+    _pass_lib(radar)
     r = radar.contiguous().float()
     B, C, R, _ = r.shape
     with torch.cuda.device(r.device):
@@ -36,7 +34,7 @@ def preprocess_input_radar(radar, dtype=torch.float32):
 
 
 def normalize_points(points, dtype=torch.float32):
-    _need_gpu(points, 'normalize_points')
+    _pass_lib(points)
     p = points.contiguous().float()
     B, N, D = p.shape
     with torch.cuda.device(p.device):
@@ -46,7 +44,7 @@ def normalize_points(points, dtype=torch.float32):
 
 
 def preprocess_input(images_u8, dtype=torch.float32):
-    _need_gpu(images_u8, 'preprocess_input')
+    _pass_lib(images_u8)
     x = images_u8.contiguous()
     if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
         raise ValueError("expected uint8 images [B,R,R,3]")
@@ -58,7 +56,7 @@ def preprocess_input(images_u8, dtype=torch.float32):
 
 
 def seg_class_map(seg):
-    _need_gpu(seg, 'seg_class_map')
+    _pass_lib(seg)
     s = seg.contiguous()
     B, C, R, _ = s.shape
     with torch.cuda.device(s.device):
@@ -71,7 +69,7 @@ def seg_class_map_original(seg, image_shape):
     """The class map at the ORIGINAL image size exactly as the reference's detect_image builds it (achelous.py:283-318): softmax over
     the classes, the letterbox's grey bars cropped (utils_seg/utils.py:19-31), cv2.resize(..., INTER_LINEAR) to `image_shape` = (h, w),
     argmax.  All frames of the batch share `image_shape`."""
-    _need_gpu(seg, 'seg_class_map_original')
+    _pass_lib(seg)
     s = seg.contiguous()
     B, C, R, _ = s.shape
     oh, ow = int(image_shape[0]), int(image_shape[1])
@@ -123,25 +121,15 @@ def _pil_coeffs(in_size, out_size, device):
     return _COEFFS[key]
 
 
-def _pass_lib(t):
-    lib = getattr(_pass_lib, 'test_library', None)
-    if lib is None:
-        _need_gpu(t, 'resize_image')
-        lib = _eng.hip_library()
-    return lib
-
-
 def _resample(lib, src, out_h, out_w, dst=None):
     """PIL.Image.resize((out_w, out_h), BICUBIC) of an HWC uint8 tensor; `dst` (a window of a larger canvas) receives the last pass."""
     H, W, C = src.shape
-    stream = torch.cuda.current_stream(src.device).cuda_stream if src.is_cuda else 0
+    stream = _stream(src)
 
     def run(s, oh, ow, vertical, d):
         b, k, ks = _pil_coeffs(s.shape[0] if vertical else s.shape[1], oh if vertical else ow, s.device)
-        rc = lib.lib.ach_resample_pass_u8(s.data_ptr(), d.data_ptr(), b.data_ptr(), k.data_ptr(), ks, s.shape[0], s.shape[1], oh, ow, C, int(vertical),
-                                          s.stride(0), d.stride(0), stream)
-        if rc != 0:
-            raise RuntimeError((lib.lib.ach_last_error(None) or b'resample pass failed').decode())
+        _check(lib, lib.lib.ach_resample_pass_u8(s.data_ptr(), d.data_ptr(), b.data_ptr(), k.data_ptr(), ks, s.shape[0], s.shape[1], oh, ow, C, int(vertical),
+                                                 s.stride(0), d.stride(0), stream), what='resample pass')
         return d
 
     cur = src
@@ -207,24 +195,12 @@ PALETTE_SEG = ((0, 0, 0), (128, 0, 0), (0, 128, 0), (128, 128, 0), (0, 0, 128), 
 PALETTE_LINE = tuple(reversed(PALETTE_SEG))
 SERVE_TABLE_COLS = 16        # k_serve.h
 _SERVE_OUTPUTS = ('semantic', 'waterline', 'overlay')
-_frame_handles = {}
 
 
 def _frames_handle(t, R, dtype):
-    """the engine handle whose softmax serves tensors like `t` (tests: the emulation library through `_pass_lib.test_library`)"""
-    lib = getattr(_pass_lib, 'test_library', None)
-    if lib is None:
-        _need_gpu(t, 'a ragged-batch call')
-        return _handle(1, R, dtype)
-    code = {torch.float32: _eng.DTYPE_F32, torch.bfloat16: _eng.DTYPE_BF16, torch.float16: _eng.DTYPE_F16}[dtype]
-    if (R, code) not in _frame_handles:
-        _frame_handles[(R, code)] = _eng.NativeEngine(lib, num_det=1, num_seg=1, phi='S0', backbone='en', resolution=R, pc_channels=3, pc_classes=1, num_points=16,
-                                                      nano_head=True, spp=True, dtype=code)
-    return _frame_handles[(R, code)]
-
-
-def _stream_of(t):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+    """the engine handle whose kernels serve tensors like `t` (tests: the emulation library through `_pass_lib.test_library`)"""
+    _pass_lib(t)
+    return stateless_handle(1, R, dtype, getattr(_pass_lib, 'test_library', None))
 
 
 def _frame_shapes(shapes, B):
@@ -331,7 +307,7 @@ def _seg_maps_plan(se, lane, shapes, arena=None, palette_se=PALETTE_SEG, palette
         with ctx:
             h.seg_overlay_frames(B, C, s, ln, ws_se, ws_line, arena.data if 'overlay' in want else None, arena.data.numel() if 'overlay' in want else 0,
                                  *addr(tref), *addr(consts), n_se, n_line, blend[0], blend[1], brightness is not None, arenas.get('semantic'), nbytes('semantic'),
-                                 arenas.get('waterline'), nbytes('waterline'), arenas.get('overlay'), nbytes('overlay'), _stream_of(s))
+                                 arenas.get('waterline'), nbytes('waterline'), arenas.get('overlay'), nbytes('overlay'), _stream(s).value)
         res = {'arenas': arenas}
         for name in want:
             a = arenas[name]
@@ -378,7 +354,7 @@ def correct_boxes_frames(rows, cnt, input_shape, shapes, letterbox_image):
     h = _frames_handle(rows, R, torch.float32)
     ctx = torch.cuda.device(rows.device) if rows.is_cuda else contextlib.nullcontext()
     with ctx:
-        h.correct_boxes_frames(B, max_det, rows, cnt.contiguous(), meta.host_ptr(ref).value, meta.dev_ptr(ref).value, letterbox_image, out, _stream_of(rows))
+        h.correct_boxes_frames(B, max_det, rows, cnt.contiguous(), meta.host_ptr(ref).value, meta.dev_ptr(ref).value, letterbox_image, out, _stream(rows).value)
     return out
 
 

@@ -5,34 +5,22 @@ streams and the autograd tape only (views, `cat`, slices and residual adds betwe
 `achelous_amd/train_graph.py` composes them into `Achelous.forward` for `.train()` (the reference runs the same
 arithmetic through ATen autograd, utils/utils_fit.py:37-166).  No PyTorch-op or CPU fallback: without the HIP library these raise.
 """
-import ctypes
+import os
 
 import torch
 
-from .train_ops import _lib, _check, _p, _stream, _bn_train_fwd, _LinearFn
+from ._native import NULL as _NULL, lib as _lib, check as _check, ptr as _p, stream as _stream, f32c as _f32, empty as _empty, prec as _prec
+from ._native import gemm_batched, gemm_dw, gemm_w_cols, gemm_wt_dz
+from .train_ops import _bn_train_fwd, _bn_train_bwd, _LinearFn
 
-_NULL = ctypes.c_void_p()
 ACT_RELU, ACT_SILU, ACT_GELU, ACT_SIGMOID = 0, 1, 2, 3
 
 
-def _f32(t, what):
-    if t.dtype != torch.float32:
-        raise TypeError(f"{what}: the training kernels are float32 (got {t.dtype})")
-    return t.contiguous()
-
-
-def _empty(like, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=like.device)
-
-
-def _prec(lib):
-    """The operand type a training forward runs its GEMMs with (ach_train_set_gemm_precision, set by the module's forward): recorded on the autograd ctx so that the
-    node's backward launches use the same one whatever another module or thread has set meanwhile (ach_train_gemm_p)."""
-    return int(lib.lib.ach_train_get_gemm_precision())
-
-
-def _gemm(lib, s, A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, tA, tB, batch, reduce=0, acc=0, bias=None, prec=-1):
-    _check(lib, lib.lib.ach_train_gemm_p(_p(A), _p(B), _p(C), _p(bias) if bias is not None else _NULL, M, N, K, lda, ldb, ldc, sA, sB, sC, tA, tB, batch, reduce, acc, int(prec), s))
+def _bias_grad(lib, s, dy, B, C, n):
+    """db[c] = the sum of dy [B, C, n] over (B, n): one row-reduce launch, then a tiny sum over the batch"""
+    per = _empty(dy, B * C)
+    _check(lib, lib.lib.ach_train_row_reduce(_p(dy), _NULL, _p(per), B * C, n, 1.0, s))
+    return per.view(B, C).sum(0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ element-wise
@@ -163,7 +151,7 @@ class _BatchNormFn(torch.autograd.Function):
         x = _f32(x, 'batchnorm')
         lib = _lib(x)
         g = gamma.detach().contiguous()
-        y, mean, var = _bn_train_fwd(lib, lib.lib, _stream(x), x, g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
+        y, mean, var = _bn_train_fwd(lib, _stream(x), x, g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
         ctx.save_for_backward(x, y, mean, var, g)
         ctx.cfg = (training, float(eps), int(relu))
         return y
@@ -174,11 +162,7 @@ class _BatchNormFn(torch.autograd.Function):
         training, eps, relu = ctx.cfg
         if not training:
             raise NotImplementedError("BatchNorm backward is built for training mode (batch statistics)")
-        B, C, N = x.shape
-        lib = _lib(x)
-        dg, db, dx = _empty(x, C), _empty(x, C), torch.empty_like(x)
-        dy = dy.contiguous()              # bound to a name: a temporary would be freed before the kernel reads it
-        _check(lib, lib.lib.ach_train_bn_relu_bwd(_p(x), _p(y), _p(dy), _p(mean), _p(var), _p(g), _p(dg), _p(db), _p(dx), B, C, N, eps, relu, _stream(x)))
+        dx, dg, db = _bn_train_bwd(_lib(x), _stream(x), x, y, dy.contiguous(), mean, var, g, eps, relu)
         return dx, dg, db, None, None, None, None, None, None
 
 
@@ -313,8 +297,7 @@ def _pair(v):
 # The switch: environment variable ACHELOUS_KEEP_COLUMN_BYTES (read at import) or `achelous_amd.train_functional.KEEP_COLUMN_BYTES = n` at run time.
 # The kept buffer is a plain ctx attribute, not save_for_backward: it is OVERWRITTEN by the column gradient in the backward, which saved-tensor hooks (checkpointing,
 # CPU offload) must not see as a saved activation; with such hooks installed set the limit to 0.
-import os as _os
-KEEP_COLUMN_BYTES = int(_os.environ.get('ACHELOUS_KEEP_COLUMN_BYTES', 1 << 30))
+KEEP_COLUMN_BYTES = int(os.environ.get('ACHELOUS_KEEP_COLUMN_BYTES', 1 << 30))
 
 
 class _Conv2dFn(torch.autograd.Function):
@@ -342,7 +325,7 @@ class _Conv2dFn(torch.autograd.Function):
         w2 = weight.detach().reshape(Co, K).contiguous()
         y = _empty(x, B, Co, Ho, Wo)
         ctx.prec = _prec(lib)
-        _gemm(lib, s, w2, col, y, Co, O, K, K, O, O, 0, K * O, Co * O, 0, 0, B, bias=bias.detach().contiguous() if bias is not None else None, prec=ctx.prec)
+        gemm_w_cols(lib, s, w2, col, y, bias.detach().contiguous() if bias is not None else None, ctx.prec)
         ctx.save_for_backward(x, w2)
         ctx.cfg = (cfg, direct, bias is not None, tuple(weight.shape))
         ctx.col = col if (not direct and col.numel() * 4 <= KEEP_COLUMN_BYTES) else None
@@ -366,22 +349,17 @@ class _Conv2dFn(torch.autograd.Function):
             col = _empty(x, B, K, O)
             _check(lib, L.ach_train_im2col(_p(x), _p(col), *cfg, 0, s))
         dw = _empty(x, *wshape)                      # dW = sum_b dy[b] col[b]^T  ([Co, K] in memory; allocated in the parameter's shape: a view would make AccumulateGrad clone it)
-        _gemm(lib, s, dy, col, dw, Co, K, O, O, O, K, Co * O, K * O, 0, 0, 1, B, reduce=1, prec=ctx.prec)
+        gemm_dw(lib, s, dy, col, dw, ctx.prec)
         dx = None
         if ctx.needs_input_grad[0]:
             dcol = torch.empty_like(x) if direct else col                     # dcol[b] = W^T dy[b]  (over the column buffer: the weight gradient above was its last reader, in stream order)
-            _gemm(lib, s, w2, dy, dcol, K, O, Co, K, O, O, 0, Co * O, K * O, 1, 0, B, prec=ctx.prec)
+            gemm_wt_dz(lib, s, w2, dy, dcol, ctx.prec)
             if direct:
                 dx = dcol
             else:
                 dx = torch.empty_like(x)
                 _check(lib, L.ach_train_im2col(_p(dcol), _p(dx), *cfg, 1, s))
-        db = None
-        if has_bias:
-            per = _empty(x, B * Co)
-            _check(lib, L.ach_train_row_reduce(_p(dy), _NULL, _p(per), B * Co, O, 1.0, s))
-            db = per.view(B, Co).sum(0)
-        return dx, dw, db, None, None
+        return dx, dw, _bias_grad(lib, s, dy, B, Co, O) if has_bias else None, None, None
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0):
@@ -409,7 +387,7 @@ class _DWConvFn(torch.autograd.Function):
         w2 = weight.detach().reshape(C, k * k).contiguous()
         y = torch.empty_like(x)
         bs = bias.detach().contiguous() if bias is not None else None
-        _check(lib, lib.lib.ach_train_dwconv(_p(x), _p(w2), _p(bs) if bs is not None else _NULL, _p(y), B, C, H, W, k, 0, _stream(x)))
+        _check(lib, lib.lib.ach_train_dwconv(_p(x), _p(w2), _p(bs), _p(y), B, C, H, W, k, 0, _stream(x)))
         ctx.save_for_backward(x, w2)
         ctx.cfg = (k, bias is not None)
         return y
@@ -426,12 +404,7 @@ class _DWConvFn(torch.autograd.Function):
         _check(lib, L.ach_train_dwconv(_p(dy), _p(w2), _NULL, _p(dx), B, C, H, W, k, 1, s))
         dw = _empty(x, C, 1, k, k)
         _check(lib, L.ach_train_dwconv_wgrad(_p(x), _p(dy), _p(dw), B, C, H, W, k, s))
-        db = None
-        if has_bias:
-            per = _empty(x, B * C)
-            _check(lib, L.ach_train_row_reduce(_p(dy), _NULL, _p(per), B * C, H * W, 1.0, s))
-            db = per.view(B, C).sum(0)
-        return dx, dw, db
+        return dx, dw, _bias_grad(lib, s, dy, B, C, H * W) if has_bias else None
 
 
 def dwconv(x, weight, bias=None):
@@ -444,12 +417,10 @@ class _BmmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, nt):
         a, b = _f32(a, 'bmm'), _f32(b, 'bmm')
-        T, M, K = a.shape
-        N = b.shape[1] if nt else b.shape[2]
         lib = _lib(a)
-        c = _empty(a, T, M, N)
+        c = _empty(a, a.shape[0], a.shape[1], b.shape[1] if nt else b.shape[2])
         ctx.prec = _prec(lib)
-        _gemm(lib, _stream(a), a, b, c, M, N, K, K, K if nt else N, N, M * K, b.shape[1] * b.shape[2], M * N, 0, 1 if nt else 0, T, prec=ctx.prec)
+        gemm_batched(lib, _stream(a), a, b, c, False, nt, ctx.prec)
         ctx.save_for_backward(a, b)
         ctx.nt = nt
         return c
@@ -458,18 +429,16 @@ class _BmmFn(torch.autograd.Function):
     def backward(ctx, dc):
         a, b = ctx.saved_tensors
         nt = ctx.nt
-        T, M, K = a.shape
-        N = b.shape[1] if nt else b.shape[2]
         lib = _lib(a)
         s = _stream(a)
         dc = dc.contiguous()
         da, db = torch.empty_like(a), torch.empty_like(b)
         if nt:       # C = A B^T: dA = dC B ; dB = dC^T A
-            _gemm(lib, s, dc, b, da, M, K, N, N, K, K, M * N, N * K, M * K, 0, 0, T, prec=ctx.prec)
-            _gemm(lib, s, dc, a, db, N, K, M, N, K, K, M * N, M * K, N * K, 1, 0, T, prec=ctx.prec)
+            gemm_batched(lib, s, dc, b, da, False, False, ctx.prec)
+            gemm_batched(lib, s, dc, a, db, True, False, ctx.prec)
         else:        # C = A B: dA = dC B^T ; dB = A^T dC
-            _gemm(lib, s, dc, b, da, M, K, N, N, N, K, M * N, K * N, M * K, 0, 1, T, prec=ctx.prec)
-            _gemm(lib, s, a, dc, db, K, N, M, K, N, N, M * K, M * N, K * N, 1, 0, T, prec=ctx.prec)
+            gemm_batched(lib, s, dc, b, da, False, True, ctx.prec)
+            gemm_batched(lib, s, a, dc, db, True, False, ctx.prec)
         return da, db, None
 
 
@@ -584,7 +553,7 @@ class _DeformConvFn(torch.autograd.Function):
         w2 = weight.detach().reshape(Co, K).contiguous()
         y = _empty(x, B, Co, Ho, Wo)
         ctx.prec = _prec(lib)
-        _gemm(lib, s, w2, col, y, Co, O, K, K, O, O, 0, K * O, Co * O, 0, 0, B, prec=ctx.prec)
+        gemm_w_cols(lib, s, w2, col, y, None, ctx.prec)
         ctx.save_for_backward(x, offset, mask, w2)
         ctx.cfg = (Ho, Wo, stride, pad, tuple(weight.shape))
         ctx.col = col if col.numel() * 4 <= KEEP_COLUMN_BYTES else None
@@ -595,7 +564,7 @@ class _DeformConvFn(torch.autograd.Function):
         x, offset, mask, w2 = ctx.saved_tensors
         Ho, Wo, stride, pad, wshape = ctx.cfg
         B, C, H, W = x.shape
-        Co, K, O = w2.shape[0], w2.shape[1], Ho * Wo
+        K, O = w2.shape[1], Ho * Wo
         lib = _lib(x)
         L, s = lib.lib, _stream(x)
         dy = dy.contiguous()
@@ -605,12 +574,12 @@ class _DeformConvFn(torch.autograd.Function):
             col = _empty(x, B, K, O)
             _check(lib, L.ach_train_deform_im2col(_p(x), _p(offset), _p(mask), _p(col), B, C, H, W, Ho, Wo, stride, pad, s))
         dw = _empty(x, *wshape)
-        _gemm(lib, s, dy, col, dw, Co, K, O, O, O, K, Co * O, K * O, 0, 0, 1, B, reduce=1, prec=ctx.prec)
+        gemm_dw(lib, s, dy, col, dw, ctx.prec)
         dcol = col                                                                # reuse the buffer
-        _gemm(lib, s, w2, dy, dcol, K, O, Co, K, O, O, 0, Co * O, K * O, 1, 0, B, prec=ctx.prec)
+        gemm_wt_dz(lib, s, w2, dy, dcol, ctx.prec)
         dx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None             # (the first RCBlock samples the pooled radar map: an input, no gradient — 354 M atomic adds at batch 32)
         doff, dmask = torch.empty_like(offset), torch.empty_like(mask)
-        _check(lib, L.ach_train_deform_bwd(_p(x), _p(offset), _p(mask), _p(dcol), _p(dx) if dx is not None else _NULL, _p(doff), _p(dmask), B, C, H, W, Ho, Wo, stride, pad, s))
+        _check(lib, L.ach_train_deform_bwd(_p(x), _p(offset), _p(mask), _p(dcol), _p(dx), _p(doff), _p(dmask), B, C, H, W, Ho, Wo, stride, pad, s))
         return dx, doff, dmask, dw, None, None
 
 
@@ -673,7 +642,7 @@ class _Pn2InterpFn(torch.autograd.Function):
         C1 = sk.shape[2] if sk is not None else 0
         lib = _lib(xyz1)
         out = _empty(xyz1, B * n, C1 + C2)
-        _check(lib, lib.lib.ach_train_pn2_interp(_p(xyz1), _p(xyz2), _p(sk) if sk is not None else _NULL, C1, _p(sparse), C2, _p(out), _NULL, _NULL, _NULL, B, n, s, _stream(xyz1)))
+        _check(lib, lib.lib.ach_train_pn2_interp(_p(xyz1), _p(xyz2), _p(sk), C1, _p(sparse), C2, _p(out), _NULL, _NULL, _NULL, B, n, s, _stream(xyz1)))
         ctx.save_for_backward(xyz1, xyz2)
         ctx.dims = (B, n, s, C1, C2)
         return out
@@ -686,7 +655,7 @@ class _Pn2InterpFn(torch.autograd.Function):
         dout = dout.contiguous()
         dskip = _empty(dout, B, n, C1) if C1 else None
         dsparse = torch.zeros(B, s, C2, dtype=torch.float32, device=dout.device)
-        _check(lib, lib.lib.ach_train_pn2_interp(_p(xyz1), _p(xyz2), _NULL, C1, _NULL, C2, _NULL, _p(dskip) if dskip is not None else _NULL, _p(dsparse), _p(dout), B, n, s, _stream(dout)))
+        _check(lib, lib.lib.ach_train_pn2_interp(_p(xyz1), _p(xyz2), _NULL, C1, _NULL, C2, _NULL, _p(dskip), _p(dsparse), _p(dout), B, n, s, _stream(dout)))
         return None, None, dskip, dsparse
 
 

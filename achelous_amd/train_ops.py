@@ -19,22 +19,15 @@ batch statistics; normalise + ReLU; their backward).  In training mode it normal
 mode it uses the running statistics.  Parameter names (`conv.weight [cout,cin,1]`, `conv.bias`, `bn.weight`, ...) are those of the
 torch layers it replaces.  fp32 on GPU tensors only; no PyTorch-op or CPU fallback.  (`Achelous.forward` in `.train()` composes these with train_functional.py's primitives for the whole model: train_graph.py.)
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
-from . import engine as _eng
-
-
-def _lib(t):
-    if not t.is_cuda and not getattr(_lib, 'test_library', None):
-        raise RuntimeError("achelous_amd.train_ops needs GPU tensors (HIP kernels; there is no CPU path)")
-    return getattr(_lib, 'test_library', None) or _eng.hip_library()
+from ._native import NULL, gemm_batched, gemm_dw, gemm_w_cols, gemm_wt_dz, prec as _prec
+from ._native import lib as _lib, check as _check, ptr as _p, stream as _stream      # (under these names for tests and profiles/scripts: the definitions are _native's)
 
 
 def set_gemm_precision(t, precision):
-    """Operand type of every `ach_train_gemm` from now on, process-wide: 0 = fp32 MFMA, 1 = operands rounded to bf16 while staged, fp32
+    """Operand type of every training GEMM from now on, process-wide: 0 = fp32 MFMA, 1 = operands rounded to bf16 while staged, fp32
     accumulation (include/achelous.h).  `t`: any tensor of the device the step runs on (selects the library as `_lib` does).  Returns the previous value."""
     L = _lib(t).lib
     prev = L.ach_train_get_gemm_precision()
@@ -43,24 +36,39 @@ def set_gemm_precision(t, precision):
     return prev
 
 
-def _check(lib, rc):
-    if rc != 0:
-        raise RuntimeError((lib.lib.ach_last_error(None) or b'train kernel failed').decode())
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0)
-
-
-def _update_running(lib, L, s, mean, var, running_mean, running_var, momentum, m):
+def _update_running(lib, s, mean, var, running_mean, running_var, momentum, m):
     """nn.BatchNorm's running-estimate update as ONE native launch (it was four element-wise torch launches per layer)."""
     if running_mean.dtype != torch.float32 or running_var.dtype != torch.float32 or not running_mean.is_contiguous() or not running_var.is_contiguous():
         raise TypeError("BatchNorm running statistics must be contiguous float32 tensors")
-    _check(lib, L.ach_train_bn_running(_p(mean), _p(var), _p(running_mean), _p(running_var), mean.numel(), float(momentum), float(m) / float(max(m - 1, 1)), s))
+    _check(lib, lib.lib.ach_train_bn_running(_p(mean), _p(var), _p(running_mean), _p(running_var), mean.numel(), float(momentum), float(m) / float(max(m - 1, 1)), s))
+
+
+def _bn_train_fwd(lib, s, z3, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
+    """Shared tail of the conv + BatchNorm [+ ReLU] Functions on z3 [B, C, N]: statistics, running update (nn.BatchNorm: running <- (1 - m) running + m batch,
+    unbiased variance), normalise."""
+    B, C, N = z3.shape
+    mean = torch.empty(C, dtype=torch.float32, device=z3.device)
+    var = torch.empty(C, dtype=torch.float32, device=z3.device)
+    if training:
+        _check(lib, lib.lib.ach_train_bn_stats(_p(z3), _p(mean), _p(var), B, C, N, s))
+        if running_mean is not None:
+            _update_running(lib, s, mean, var, running_mean, running_var, momentum, B * N)
+    else:
+        mean.copy_(running_mean)
+        var.copy_(running_var)
+    y = torch.empty_like(z3)
+    _check(lib, lib.lib.ach_train_bn_relu_fwd(_p(z3), _p(mean), _p(var), _p(gamma), _p(beta), _p(y), B, C, N, float(eps), int(relu), s))
+    return y, mean, var
+
+
+def _bn_train_bwd(lib, s, z3, y, dy, mean, var, gamma, eps, relu):
+    """Backward of `_bn_train_fwd` in training mode on z3 [B, C, N] (dy contiguous) -> (dz, dgamma, dbeta)"""
+    B, C, N = z3.shape
+    dgamma = torch.empty(C, dtype=torch.float32, device=z3.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=z3.device)
+    dz = torch.empty_like(z3)
+    _check(lib, lib.lib.ach_train_bn_relu_bwd(_p(z3), _p(y), _p(dy), _p(mean), _p(var), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), B, C, N, eps, relu, s))
+    return dz, dgamma, dbeta
 
 
 class _SharedMLP1dFn(torch.autograd.Function):
@@ -74,26 +82,14 @@ class _SharedMLP1dFn(torch.autograd.Function):
         cout = weight.shape[0]
         w2 = weight.detach().reshape(cout, cin).contiguous()
         lib = _lib(x)
-        L, s = lib.lib, _stream(x)
+        s = _stream(x)
         z = torch.empty(B, cout, N, dtype=torch.float32, device=x.device)
         bs = bias.detach().contiguous() if bias is not None else None           # bound to a name: a temporary would be freed before the kernel reads it
-        ctx.prec = int(L.ach_train_get_gemm_precision())      # recorded for this node's backward launches (ach_train_gemm_p)
-        _check(lib, L.ach_train_gemm_p(_p(w2), _p(x), _p(z), _p(bs) if bs is not None else ctypes.c_void_p(), cout, N, cin,
-                                     cin, N, N, 0, cin * N, cout * N, 0, 0, B, 0, 0, ctx.prec, s))
-        mean = torch.empty(cout, dtype=torch.float32, device=x.device)
-        var = torch.empty(cout, dtype=torch.float32, device=x.device)
-        if training:
-            _check(lib, L.ach_train_bn_stats(_p(z), _p(mean), _p(var), B, cout, N, s))
-            if running_mean is not None:
-                _update_running(lib, L, s, mean, var, running_mean, running_var, momentum, B * N)      # nn.BatchNorm1d: running <- (1 - m) running + m batch, unbiased variance
-        else:
-            mean.copy_(running_mean)
-            var.copy_(running_var)
-        y = torch.empty_like(z)
-        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
-        _check(lib, L.ach_train_bn_relu_fwd(_p(z), _p(mean), _p(var), _p(gm), _p(bt), _p(y),
-                                            B, cout, N, float(eps), int(relu), s))
-        ctx.save_for_backward(x, w2, z, y, mean, var, gamma.detach().contiguous())
+        ctx.prec = _prec(lib)
+        gemm_w_cols(lib, s, w2, x, z, bs, ctx.prec)
+        g = gamma.detach().contiguous()
+        y, mean, var = _bn_train_fwd(lib, s, z, g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
+        ctx.save_for_backward(x, w2, z, y, mean, var, g)
         ctx.cfg = (training, float(eps), int(relu), bias is not None, tuple(weight.shape))
         return y
 
@@ -103,21 +99,15 @@ class _SharedMLP1dFn(torch.autograd.Function):
         training, eps, relu, has_bias, wshape = ctx.cfg
         if not training:
             raise NotImplementedError("SharedMLP1d backward is built for training mode (batch statistics)")
-        B, cin, N = x.shape
-        cout = w2.shape[0]
         lib = _lib(x)
-        L, s = lib.lib, _stream(x)
-        dy = dy.contiguous()
-        dgamma = torch.empty(cout, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(cout, dtype=torch.float32, device=x.device)
-        dz = torch.empty_like(z)
-        _check(lib, L.ach_train_bn_relu_bwd(_p(z), _p(y), _p(dy), _p(mean), _p(var), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), B, cout, N, eps, relu, s))
-        dx = torch.empty_like(x)            # dx[b] = W^T dz[b]: A = W stored [cout, cin] = K x M
-        _check(lib, L.ach_train_gemm_p(_p(w2), _p(dz), _p(dx), ctypes.c_void_p(), cin, N, cout, cin, N, N, 0, cout * N, cin * N, 1, 0, B, 0, 0, ctx.prec, s))
-        dw = torch.empty(wshape, dtype=torch.float32, device=x.device)          # dW = sum_b dz[b] x[b]^T: B = x[b] stored [cin, N] = N x K; in the parameter's own shape (a VIEW of a 2-D buffer would make AccumulateGrad clone it: one copy per parameter and step)
-        _check(lib, L.ach_train_gemm_p(_p(dz), _p(x), _p(dw), ctypes.c_void_p(), cout, cin, N, N, N, cin, cout * N, cin * N, 0, 0, 1, B, 1, 0, ctx.prec, s))
+        s = _stream(x)
+        dz, dgamma, dbeta = _bn_train_bwd(lib, s, z, y, dy.contiguous(), mean, var, gamma, eps, relu)
+        dx = torch.empty_like(x)
+        gemm_wt_dz(lib, s, w2, dz, dx, ctx.prec)
+        dw = torch.empty(wshape, dtype=torch.float32, device=x.device)          # in the parameter's own shape (a VIEW of a 2-D buffer would make AccumulateGrad clone it: one copy per parameter and step)
+        gemm_dw(lib, s, dz, x, dw, ctx.prec)
         # a bias in front of a training-mode BatchNorm has zero gradient: the batch mean it shifts is subtracted again (sum dz = 0)
-        dbias = torch.zeros(cout, dtype=torch.float32, device=x.device) if has_bias else None
+        dbias = torch.zeros(w2.shape[0], dtype=torch.float32, device=x.device) if has_bias else None
         return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -138,23 +128,6 @@ class SharedMLP1d(nn.Module):
                                     self.training, bn.momentum, bn.eps, self.relu)
 
 
-def _bn_train_fwd(lib, L, s, z3, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
-    """Shared tail of the conv + BatchNorm [+ ReLU] Functions on z3 [B, C, N]: statistics, running update, normalise."""
-    B, C, N = z3.shape
-    mean = torch.empty(C, dtype=torch.float32, device=z3.device)
-    var = torch.empty(C, dtype=torch.float32, device=z3.device)
-    if training:
-        _check(lib, L.ach_train_bn_stats(_p(z3), _p(mean), _p(var), B, C, N, s))
-        if running_mean is not None:
-            _update_running(lib, L, s, mean, var, running_mean, running_var, momentum, B * N)
-    else:
-        mean.copy_(running_mean)
-        var.copy_(running_var)
-    y = torch.empty_like(z3)
-    _check(lib, L.ach_train_bn_relu_fwd(_p(z3), _p(mean), _p(var), _p(gamma), _p(beta), _p(y), B, C, N, float(eps), int(relu), s))
-    return y, mean, var
-
-
 class _DWConvBNFn(torch.autograd.Function):
     """depthwise 3x3 (stride 1, pad 1, no bias) + BatchNorm2d [+ ReLU] on [B, C, H, W]"""
 
@@ -172,7 +145,7 @@ class _DWConvBNFn(torch.autograd.Function):
         z = torch.empty_like(x)
         _check(lib, L.ach_train_dw3x3(_p(x), _p(w2), _p(z), B, C, H, W, 0, s))
         g = gamma.detach().contiguous()
-        y, mean, var = _bn_train_fwd(lib, L, s, z.view(B, C, H * W), g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
+        y, mean, var = _bn_train_fwd(lib, s, z.view(B, C, H * W), g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
         ctx.save_for_backward(x, w2, z, y, mean, var, g)
         ctx.cfg = (training, float(eps), int(relu))
         return y.view(B, C, H, W)
@@ -186,11 +159,7 @@ class _DWConvBNFn(torch.autograd.Function):
         B, C, H, W = x.shape
         lib = _lib(x)
         L, s = lib.lib, _stream(x)
-        dy = dy.contiguous()
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-        dz = torch.empty_like(z)
-        _check(lib, L.ach_train_bn_relu_bwd(_p(z), _p(y), _p(dy), _p(mean), _p(var), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), B, C, H * W, eps, relu, s))
+        dz, dgamma, dbeta = _bn_train_bwd(lib, s, z.view(B, C, H * W), y, dy.contiguous(), mean, var, gamma, eps, relu)
         dx = torch.empty_like(x)
         _check(lib, L.ach_train_dw3x3(_p(dz), _p(w2), _p(dx), B, C, H, W, 1, s))                    # mirrored taps
         dw = torch.empty(C, 1, 3, 3, dtype=torch.float32, device=x.device)
@@ -263,12 +232,10 @@ class _LinearFn(torch.autograd.Function):
         cout = weight.shape[0]
         w2 = weight.detach().reshape(cout, cin).contiguous()
         lib = _lib(x)
-        L, s = lib.lib, _stream(x)
         z = torch.empty(B, cout, N, dtype=torch.float32, device=x.device)
         bs = bias.detach().contiguous() if bias is not None else None           # bound to a name: a temporary would be freed before the kernel reads it
-        ctx.prec = int(L.ach_train_get_gemm_precision())      # recorded for this node's backward launches (ach_train_gemm_p)
-        _check(lib, L.ach_train_gemm_p(_p(w2), _p(x), _p(z), _p(bs) if bs is not None else ctypes.c_void_p(), cout, N, cin,
-                                     cin, N, N, 0, cin * N, cout * N, 0, 0, B, 0, 0, ctx.prec, s))
+        ctx.prec = _prec(lib)
+        gemm_w_cols(lib, _stream(x), w2, x, z, bs, ctx.prec)
         ctx.save_for_backward(x, w2)
         ctx.cfg = (bias is not None, tuple(weight.shape))
         return z
@@ -277,15 +244,14 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, dz):
         x, w2 = ctx.saved_tensors
         has_bias, wshape = ctx.cfg
-        B, cin, N = x.shape
-        cout = w2.shape[0]
+        B, cout, N = dz.shape
         lib = _lib(x)
         L, s = lib.lib, _stream(x)
         dz = dz.contiguous()
         dx = torch.empty_like(x)
-        _check(lib, L.ach_train_gemm_p(_p(w2), _p(dz), _p(dx), ctypes.c_void_p(), cin, N, cout, cin, N, N, 0, cout * N, cin * N, 1, 0, B, 0, 0, ctx.prec, s))
+        gemm_wt_dz(lib, s, w2, dz, dx, ctx.prec)
         dw = torch.empty(wshape, dtype=torch.float32, device=x.device)          # (in the parameter's own shape: a VIEW of a 2-D buffer would make autograd's AccumulateGrad clone it — one copy per parameter and step)
-        _check(lib, L.ach_train_gemm_p(_p(dz), _p(x), _p(dw), ctypes.c_void_p(), cout, cin, N, N, N, cin, cout * N, cin * N, 0, 0, 1, B, 1, 0, ctx.prec, s))
+        gemm_dw(lib, s, dz, x, dw, ctx.prec)
         db = None
         if has_bias:                      # db[c] = sum over (B, N) of dz = B N x the per-channel mean the statistics kernel returns
             db = torch.empty(cout, dtype=torch.float32, device=x.device)
@@ -301,26 +267,22 @@ class _BmmPointsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, T):
         x, T = x.contiguous(), T.contiguous()
-        B, K, N = x.shape
         lib = _lib(x)
-        L, s = lib.lib, _stream(x)
         y = torch.empty_like(x)
-        ctx.prec = int(L.ach_train_get_gemm_precision())      # recorded for this node's backward launches (ach_train_gemm_p)
-        _check(lib, L.ach_train_gemm_p(_p(T), _p(x), _p(y), ctypes.c_void_p(), K, N, K, K, N, N, K * K, K * N, K * N, 1, 0, B, 0, 0, ctx.prec, s))
+        ctx.prec = _prec(lib)
+        gemm_batched(lib, _stream(x), T, x, y, True, False, ctx.prec)
         ctx.save_for_backward(x, T)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, T = ctx.saved_tensors
-        B, K, N = x.shape
         lib = _lib(x)
-        L, s = lib.lib, _stream(x)
+        s = _stream(x)
         dy = dy.contiguous()
-        dx = torch.empty_like(x)                                   # dx[b] = T[b] dy[b]
-        _check(lib, L.ach_train_gemm_p(_p(T), _p(dy), _p(dx), ctypes.c_void_p(), K, N, K, K, N, N, K * K, K * N, K * N, 0, 0, B, 0, 0, ctx.prec, s))
-        dT = torch.empty_like(T)                                   # dT[b] = x[b] dy[b]^T
-        _check(lib, L.ach_train_gemm_p(_p(x), _p(dy), _p(dT), ctypes.c_void_p(), K, K, N, N, N, K, K * N, K * N, K * K, 0, 1, B, 0, 0, ctx.prec, s))
+        dx, dT = torch.empty_like(x), torch.empty_like(T)
+        gemm_batched(lib, s, T, dy, dx, False, False, ctx.prec)              # dx[b] = T[b] dy[b]
+        gemm_batched(lib, s, x, dy, dT, False, True, ctx.prec)               # dT[b] = x[b] dy[b]^T
         return dx, dT
 
 
@@ -334,7 +296,7 @@ class _MaxPointsFn(torch.autograd.Function):
         lib = _lib(x)
         y = torch.empty(B, C, dtype=torch.float32, device=x.device)
         idx = torch.empty(B, C, dtype=torch.int32, device=x.device)
-        _check(lib, lib.lib.ach_train_max_points(_p(x), _p(y), _p(idx), ctypes.c_void_p(), ctypes.c_void_p(), B * C, N, _stream(x)))
+        _check(lib, lib.lib.ach_train_max_points(_p(x), _p(y), _p(idx), NULL, NULL, B * C, N, _stream(x)))
         ctx.save_for_backward(idx)
         ctx.shape = (B, C, N)
         return y
@@ -346,7 +308,7 @@ class _MaxPointsFn(torch.autograd.Function):
         lib = _lib(dy)
         dy = dy.contiguous()
         dx = torch.empty(B, C, N, dtype=torch.float32, device=dy.device)
-        _check(lib, lib.lib.ach_train_max_points(ctypes.c_void_p(), ctypes.c_void_p(), _p(idx), _p(dy), _p(dx), B * C, N, _stream(dy)))
+        _check(lib, lib.lib.ach_train_max_points(NULL, NULL, _p(idx), _p(dy), _p(dx), B * C, N, _stream(dy)))
         return dx
 
 
@@ -359,7 +321,7 @@ class _LogSoftmaxPointsFn(torch.autograd.Function):
         B, K, N = z.shape
         lib = _lib(z)
         y = torch.empty(B, N, K, dtype=torch.float32, device=z.device)
-        _check(lib, lib.lib.ach_train_log_softmax(_p(z), _p(y), ctypes.c_void_p(), ctypes.c_void_p(), B, K, N, _stream(z)))
+        _check(lib, lib.lib.ach_train_log_softmax(_p(z), _p(y), NULL, NULL, B, K, N, _stream(z)))
         ctx.save_for_backward(y)
         return y
 
@@ -370,7 +332,7 @@ class _LogSoftmaxPointsFn(torch.autograd.Function):
         lib = _lib(y)
         dy = dy.contiguous()
         dz = torch.empty(B, K, N, dtype=torch.float32, device=y.device)
-        _check(lib, lib.lib.ach_train_log_softmax(ctypes.c_void_p(), _p(y), _p(dy), _p(dz), B, K, N, _stream(y)))
+        _check(lib, lib.lib.ach_train_log_softmax(NULL, _p(y), _p(dy), _p(dz), B, K, N, _stream(y)))
         return dz
 
 
