@@ -17,6 +17,7 @@
 #include "k_loss.h"
 #include "k_metrics.h"
 #include "k_data.h"
+#include "k_radarmap.h"
 #include "k_serve.h"
 
 struct ach_handle {
@@ -952,6 +953,69 @@ int ach_data_labels_batch(const uint8_t* arena, int64_t arena_bytes, const int64
         }
         ach::DataLabelParams lp{arena, reinterpret_cast<const long long*>(table_dev), tabs_dev, {png, png_w}, R, num_classes_seg, label_kind == 0 ? 1 : 0};
         ACH_LAUNCH(ach::data_labels_kernel, dim3(unsigned(ach::cdivl(long(R) * R, 256)), 2u, unsigned(B)), dim3(256), static_cast<hipStream_t>(stream), lp);
+    });
+}
+
+// ---- both radar inputs from raw point clouds (k_radarmap.h).  The host copy of the cloud table is checked against the arena — every extent, every column — and
+// the sampled row indices against every frame's n BEFORE anything is launched; a bad table is ACH_ERR_INVALID and no launch.
+static void radar_need_table(const int64_t* table_host, int32_t B, int64_t arena_elems, int64_t min_rows, const char* extent, const char* column) {
+    for (int b = 0; b < B; ++b) {
+        const int64_t* f = table_host + long(b) * ach::RADAR_TABLE_COLS;
+        const int64_t off = f[0], n = f[1], F = f[2], stride = f[3];
+        train_need(n >= min_rows && n < (1L << 40) && F >= 1 && F < (1L << 20) && stride >= F && stride < (1L << 20) && off >= 0 && off <= arena_elems &&
+                   (n == 0 || (n - 1) * stride + F <= arena_elems - off), extent);
+        for (int c = 4; c < 9; ++c) train_need(f[c] >= 0 && f[c] < F, column);
+    }
+}
+int ach_data_radar_maps(const void* arena, int64_t arena_elems, int32_t in_kind, const int64_t* table_host, const int64_t* table_dev, int32_t B, int32_t R,
+                        double cell_u, double cell_v, float* raw, float* partial, int64_t partial_floats, void* out, int32_t out_kind, void* stream) {
+    return train_guard([&] {
+        train_need(arena && table_host && table_dev && raw && B > 0 && B <= 65535 && R > 0 && arena_elems >= 0 &&
+                   (in_kind == ach::RADAR_IN_F32 || in_kind == ach::RADAR_IN_F64), "ach_data_radar_maps");
+        if (R > ach::RADAR_MAX_R) throw ach::AchError{ACH_ERR_UNSUPPORTED, "ach_data_radar_maps: a map larger than 2048 x 2048"};
+        train_need((reinterpret_cast<uintptr_t>(arena) & (in_kind == ach::RADAR_IN_F64 ? 7u : 3u)) == 0, "ach_data_radar_maps: the cloud arena is aligned to its element size");
+        train_need(std::isfinite(cell_u) && std::isfinite(cell_v) && cell_u != 0.0 && cell_v != 0.0, "ach_data_radar_maps: the cell sizes are finite and not zero");
+        const int rows = ach::radar_band_rows(R), bands = int(ach::cdivl(R, rows));
+        train_need(!out || (out_kind >= ach::DATA_F32 && out_kind <= ach::DATA_F16 && partial && partial_floats >= 2L * B * bands),
+                   "ach_data_radar_maps: the normalised map is fp32 / bf16 / fp16 (0..2) and needs 2 * B * ceil(R / band rows) floats of `partial`");
+        radar_need_table(table_host, B, arena_elems, 0, "ach_data_radar_maps: a cloud's extent passes the cloud arena", "ach_data_radar_maps: a column index is not below F");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        ach::RadarMapParams p{arena, reinterpret_cast<const long long*>(table_dev), raw, out ? partial : nullptr, cell_u, cell_v, R, rows, bands, in_kind};
+        ACH_LAUNCH(ach::radar_map_kernel, dim3(unsigned(bands), unsigned(B)), dim3(256), s, p);
+        if (!out) return;
+        const long per = 3L * R * R;
+        ach::RadarScaleParams ps{raw, partial, out, per, bands, B};
+        const dim3 grid(unsigned(ach::cdivl(per * B, 256)));
+        if (out_kind == ach::DATA_F32) ACH_LAUNCH(ach::radar_scale_kernel<float>, grid, dim3(256), s, ps);
+        else if (out_kind == ach::DATA_BF16) ACH_LAUNCH(ach::radar_scale_kernel<ach::bf16_t>, grid, dim3(256), s, ps);
+        else ACH_LAUNCH(ach::radar_scale_kernel<ach::f16_t>, grid, dim3(256), s, ps);
+    });
+}
+int ach_data_radar_points(const void* arena, int64_t arena_elems, int32_t in_kind, const int64_t* table_host, const int64_t* table_dev, const int64_t* indices_host,
+                          const int64_t* indices_dev, const int32_t* columns, int32_t D, int32_t label_column, int32_t B, int32_t N, void* points,
+                          int32_t out_kind, int64_t* labels, void* stream) {
+    return train_guard([&] {
+        train_need(arena && table_host && table_dev && indices_host && indices_dev && columns && points && B > 0 && N > 0 && arena_elems >= 0 &&
+                   (in_kind == ach::RADAR_IN_F32 || in_kind == ach::RADAR_IN_F64) && out_kind >= ach::DATA_F32 && out_kind <= ach::DATA_F16, "ach_data_radar_points");
+        train_need(D >= 1 && D <= ach::RADAR_MAX_D && long(B) * (D + 1) < (1L << 31), "ach_data_radar_points: 1..16 point columns");
+        train_need((labels != nullptr) == (label_column >= 0), "ach_data_radar_points: a label column and a label output go together");
+        train_need((reinterpret_cast<uintptr_t>(arena) & (in_kind == ach::RADAR_IN_F64 ? 7u : 3u)) == 0, "ach_data_radar_points: the cloud arena is aligned to its element size");
+        radar_need_table(table_host, B, arena_elems, 1, "ach_data_radar_points: a cloud is empty or its extent passes the cloud arena",
+                         "ach_data_radar_points: a column index is not below F");
+        ach::RadarPointsParams p{arena, reinterpret_cast<const long long*>(table_dev), reinterpret_cast<const long long*>(indices_dev), points,
+                                 reinterpret_cast<long long*>(labels), N, D, in_kind, label_column, {}};
+        for (int b = 0; b < B; ++b) {
+            const int64_t* f = table_host + long(b) * ach::RADAR_TABLE_COLS;
+            for (int d = 0; d < D; ++d) train_need(columns[d] >= 0 && columns[d] < f[2], "ach_data_radar_points: a column index is not below F");
+            train_need(label_column < f[2], "ach_data_radar_points: a column index is not below F");
+            for (long i = 0; i < N; ++i) train_need(indices_host[long(b) * N + i] >= 0 && indices_host[long(b) * N + i] < f[1], "ach_data_radar_points: a row index is not below n");
+        }
+        for (int d = 0; d < D; ++d) p.cols[d] = columns[d];
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const dim3 grid(unsigned(B * (D + 1)));
+        if (out_kind == ach::DATA_F32) ACH_LAUNCH(ach::radar_points_kernel<float>, grid, dim3(256), s, p);
+        else if (out_kind == ach::DATA_BF16) ACH_LAUNCH(ach::radar_points_kernel<ach::bf16_t>, grid, dim3(256), s, p);
+        else ACH_LAUNCH(ach::radar_points_kernel<ach::f16_t>, grid, dim3(256), s, p);
     });
 }
 

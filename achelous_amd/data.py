@@ -1,4 +1,5 @@
-"""Training batches assembled on the device from ragged frames (csrc/k_data.h; C ABI `ach_data_letterbox_batch`, `ach_data_labels_batch`).
+"""Training batches assembled on the device from ragged frames (csrc/k_data.h, csrc/k_radarmap.h; C ABI `ach_data_letterbox_batch`, `ach_data_labels_batch`,
+`ach_data_radar_maps`, `ach_data_radar_points`).
 
 The live path of the reference's `YoloDataset.__getitem__` / `get_random_data` + `yolo_dataset_collate_all` (utils/dataloader.py:87-148, 153-233, 517-550) for B decoded
 frames of different sizes at once, producing what `GraphedTrainStep` / `MultiTaskLoss.forward(outputs, boxes, counts, png, png_w, pc_labels)` and the network take:
@@ -8,7 +9,9 @@ frames of different sizes at once, producing what `GraphedTrainStep` / `MultiTas
     png, png_w [B, R, R] uint8 / int64        PIL NEAREST resize, pasted on zeros, min(v, num_classes_seg) / min(v, 2); a frame without a water-line map: zeros
     boxes [B, G, 5] fp32, counts [B] int32    the reference's integer box arithmetic in numpy on the host (a handful of numbers), packed as `losses.pack_labels` packs
     points [B, D, N], pc_labels [B, N] int64  N rows sampled with replacement on the host, then the existing `prepost.normalize_points`
-    radar   [B, C, R, R] fp32                 passes through
+    radar   [B, C, R, R] fp32                 passes through; or, for frames that carry a raw `cloud` [n, F], rasterised on the device by the rule of the reference's
+                                              radar_feature_map_generate.ipynb (`radar_maps_batch`), with `points` / `pc_labels` gathered from the same upload
+                                              (`radar_points_batch`): one launch each
 
 Per batch: two image launches, one label launch, one point launch, whatever B is; three host-to-device copies (image arena, label arena, one buffer with the frame
 tables, the coefficient / index tables, the value table, boxes, points and radar maps) from reusable pinned memory, none back.  Placement defaults to the
@@ -34,6 +37,11 @@ _ERRORS = {-1: ValueError, -2: NotImplementedError}
 
 Batch = collections.namedtuple('Batch', 'images radar points boxes counts png png_w pc_labels')
 Arena = collections.namedtuple('Arena', 'data frames')          # data: 1-D uint8 tensor on the device; frames: per frame (byte offset, H, W, pitch) or None
+Clouds = collections.namedtuple('Clouds', 'data frames')        # data: 1-D float32 / float64 tensor on the device; frames: per frame (element offset, n, F, row stride)
+RADAR_TABLE_COLS = 16    # k_radarmap.h
+MAP_COLUMNS = (0, 1, 2, 3, 4)          # the notebook's feature order: range, doppler, rcs, u, v
+CELL = (6.0, 3.375)                    # 1920 / 320 and 1080 / 320 pixels per cell: the notebook's constants, whatever the resolution
+_IN_KIND = {torch.float32: 0, torch.float64: 1}
 
 
 # ------------------------------------------------------------------------------------------------------------------ host rules
@@ -336,6 +344,123 @@ def labels_batch(png, png_w, resolution, num_classes_seg, placements=None, label
     return _launch_labels(meta, a.data, ref, len(a.frames), R, num_classes_seg, label_dtype)
 
 
+# ------------------------------------------------------------------------------------------------------------------ radar clouds (csrc/k_radarmap.h)
+def pack_clouds(clouds, device='cuda', name='clouds'):
+    """B host arrays [n_i, F_i] (all float32 or all float64; n_i may be 0) -> `Clouds`: packed into reusable pinned memory, 16-byte aligned frames, ONE copy."""
+    arrs = []
+    for b, c in enumerate(clouds):
+        a = c.numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+        if a.ndim != 2 or a.shape[1] < 1 or a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"pack_clouds: frame {b}: clouds are CPU float32 / float64 arrays [n, F]")
+        arrs.append(a)
+    if not arrs or any(a.dtype != arrs[0].dtype for a in arrs):
+        raise TypeError("pack_clouds: at least one cloud, all of one dtype")
+    item = arrs[0].dtype.itemsize
+    step = 16 // item
+    offs, total = [], 0
+    for a in arrs:
+        offs.append(total)
+        total += (a.size + step - 1) // step * step
+    total = max(total, step)
+    pin = _pinned(device)
+    slot = pin.take(name, total * item)
+    host = slot[0].numpy()[:total * item].view(arrs[0].dtype)
+    for a, o in zip(arrs, offs):
+        np.copyto(host[o:o + a.size].reshape(a.shape), a)
+    data = pin.upload(slot, total * item).view(torch.float32 if item == 4 else torch.float64)
+    return Clouds(data, [(o, a.shape[0], a.shape[1], a.shape[1]) for a, o in zip(arrs, offs)])
+
+
+def _as_clouds(clouds, device, name='clouds'):
+    return clouds if isinstance(clouds, Clouds) else pack_clouds(clouds, device, name)
+
+
+def _plan_clouds(meta, packed, columns):
+    cols = tuple(int(c) for c in columns)
+    if len(cols) != 5:
+        raise ValueError("columns: the five column indices of range, doppler, rcs, u, v")
+    table = np.zeros((len(packed.frames), RADAR_TABLE_COLS), np.int64)
+    for b, fr in enumerate(packed.frames):
+        table[b, :4] = fr
+        table[b, 4:9] = cols
+    return meta.add(table)
+
+
+def _launch_radar_maps(meta, packed, ref, R, cell, normalize, dtype):
+    data = packed.data
+    lib = _lib(data)
+    B = len(packed.frames)
+    raw = torch.empty(B, 3, R, R, dtype=torch.float32, device=data.device)
+    out = partial = None
+    if normalize:
+        if dtype not in _OUT_KIND or dtype == torch.uint8:
+            raise TypeError(f"the normalised radar map is float32, bfloat16 or float16, got {dtype}")
+        out = torch.empty(B, 3, R, R, dtype=dtype, device=data.device)
+        partial = torch.empty(2 * B * R, dtype=torch.float32, device=data.device)          # per frame one (min, max) per band of rows: at most R bands
+    _check(lib, lib.lib.ach_data_radar_maps(_p(data), data.numel(), _IN_KIND[data.dtype], meta.host_ptr(ref), meta.dev_ptr(ref), B, R, float(cell[0]), float(cell[1]),
+                                            _p(raw), _p(partial), partial.numel() if normalize else 0, _p(out), _OUT_KIND[dtype] if normalize else 0, _stream(data)),
+           _ERRORS, 'radar kernel')
+    return out if normalize else raw
+
+
+def radar_maps_batch(clouds, resolution, columns=MAP_COLUMNS, cell=CELL, normalize=False, dtype=torch.float32, device='cuda'):
+    """`clouds`: a list of CPU float32 / float64 arrays [n_i, F] (any n_i, 0 included), or `Clouds` already on the device -> the radar map [B, 3, R, R] the reference
+    generates offline (radar_feature_map_generate.ipynb), EXACTLY: per channel (range, doppler, rcs = `columns[:3]`) and point in row order, x = int(u / cell[0]),
+    y = int(v / cell[1]) in float64 with Python's truncation and negative-index wrap, the notebook's one-cell shift of a point that meets an occupied cell, later
+    points overwriting earlier ones, the value rounded once to fp32.  normalize=False: that raw map, fp32 (what the reference trains on), one launch.
+    normalize=True: `prepost.preprocess_input_radar(raw, dtype)` of it, the same bits, with the extrema taken in the rasterising pass: two launches."""
+    R = int(resolution)
+    packed = _as_clouds(clouds, device)
+    meta = _Meta(packed.data.device, 'radar')
+    ref = _plan_clouds(meta, packed, columns)
+    meta.commit()
+    return _launch_radar_maps(meta, packed, ref, R, cell, bool(normalize), dtype)
+
+
+def draw_indices(counts, num_points, indices=None, rng=None):
+    """utils/dataloader.py:137: `num_points` row indices with replacement per cloud of `counts[b]` rows, the caller's or drawn from `rng` -> int64 [B, N]"""
+    N = int(num_points)
+    if indices is None and rng is None:
+        raise ValueError("pass `indices` [B, N] or a numpy.random.Generator as `rng`")
+    out = np.empty((len(counts), N), np.int64)
+    for b, n in enumerate(counts):
+        if n < 1:
+            raise ValueError(f"frame {b} has an empty point cloud")
+        idx = np.asarray(indices[b], dtype=np.int64) if indices is not None else rng.choice(n, N, replace=True)
+        if idx.shape != (N,) or idx.min() < 0 or idx.max() >= n:
+            raise ValueError(f"frame {b} needs {N} indices below {n}")
+        out[b] = idx
+    return out
+
+
+def _launch_radar_points(meta, packed, ref, iref, columns, label_column, N, dtype):
+    data = packed.data
+    lib = _lib(data)
+    B = len(packed.frames)
+    cols = np.ascontiguousarray([int(c) for c in columns], dtype=np.int32)
+    if dtype not in _OUT_KIND or dtype == torch.uint8:
+        raise TypeError(f"points are float32, bfloat16 or float16, got {dtype}")
+    points = torch.empty(B, cols.size, N, dtype=dtype, device=data.device)
+    labels = torch.empty(B, N, dtype=torch.int64, device=data.device) if label_column is not None else None
+    _check(lib, lib.lib.ach_data_radar_points(_p(data), data.numel(), _IN_KIND[data.dtype], meta.host_ptr(ref), meta.dev_ptr(ref), meta.host_ptr(iref), meta.dev_ptr(iref),
+                                              ctypes.c_void_p(cols.ctypes.data), cols.size, -1 if label_column is None else int(label_column), B, N, _p(points),
+                                              _OUT_KIND[dtype], _p(labels), _stream(data)), _ERRORS, 'radar kernel')
+    return points, labels
+
+
+def radar_points_batch(clouds, columns, label_column=None, num_points=512, indices=None, rng=None, dtype=torch.float32, device='cuda'):
+    """The PointNet input from the same clouds (utils/dataloader.py:137-141): `num_points` rows per frame by `indices` [B, N] (or drawn with replacement from `rng`),
+    the D columns `columns`, each divided by its L2 norm over the sampled rows (sklearn normalize(axis=0); fp32 arithmetic on the fp32-rounded values, as
+    `prepost.normalize_points`) -> (points [B, D, N] `dtype`, labels [B, N] int64 from `label_column`, or None).  One launch; the indices travel with the table."""
+    packed = _as_clouds(clouds, device)
+    idx = draw_indices([f[1] for f in packed.frames], num_points, indices, rng)
+    meta = _Meta(packed.data.device, 'radar')
+    ref = _plan_clouds(meta, packed, (0,) * 5)
+    iref = meta.add(idx)
+    meta.commit()
+    return _launch_radar_points(meta, packed, ref, iref, columns, label_column, int(num_points), dtype)
+
+
 def _normalize_points(points, dtype):
     lib = getattr(_lib, 'test_library', None)
     if lib is None:
@@ -352,14 +477,20 @@ class TrainBatcher:
     `frames`: a list of dicts with `image` [H, W, 3] uint8, `png` [H, W] uint8, optionally `png_w` [H, W] uint8 (absent / None: zeros), `boxes` [n, 5] integers
     (x1, y1, x2, y2, class) in pixels of the original image, `radar` [C, R, R], and `points` [n, D] with `point_labels` [n] (all frames or none).  `placements`: one
     (nw, nh, dx, dy) per frame instead of the reference's letterbox.  Points are sampled with the caller's `indices` [B, N] or drawn from `rng`
-    (a numpy.random.Generator).  `max_boxes` fixes G (a captured graph needs fixed shapes); more surviving boxes than that is `pack_labels`' error."""
+    (a numpy.random.Generator).  `max_boxes` fixes G (a captured graph needs fixed shapes); more surviving boxes than that is `pack_labels`' error.
 
-    def __init__(self, resolution, num_classes_seg, num_points=512, dtype=torch.float32, label_dtype=torch.uint8, max_boxes=None, device='cuda'):
+    Frames with a `cloud` key (all frames or none) carry the raw radar points instead of `radar` / `points` / `point_labels`: `cloud` [n, F] float32 / float64 and
+    `cloud_columns`, a dict with 'map' (the columns of range, doppler, rcs, u, v; default 0..4) and optionally 'points' (the PointNet columns) with 'label' (the label
+    column), the same for every frame.  `radar` is then the raw map of `radar_maps_batch` (cell size `cell`), `points` / `pc_labels` come from `radar_points_batch`:
+    one upload of the clouds, one launch each."""
+
+    def __init__(self, resolution, num_classes_seg, num_points=512, dtype=torch.float32, label_dtype=torch.uint8, max_boxes=None, device='cuda', cell=CELL):
         if label_dtype not in _LABEL_KIND:
             raise TypeError(f"label maps are uint8 or int64, got {label_dtype}")
         self.R, self.num_classes_seg, self.num_points = int(resolution), int(num_classes_seg), int(num_points)
         self.dtype, self.label_dtype, self.max_boxes, self.device = _image_dtype(dtype), label_dtype, max_boxes, device
         self.point_dtype = torch.float32 if dtype == torch.uint8 else dtype
+        self.cell = (float(cell[0]), float(cell[1]))
 
     def __call__(self, frames, placements=None, indices=None, rng=None):
         R, B = self.R, len(frames)
@@ -376,6 +507,8 @@ class TrainBatcher:
         boxes, counts = pack_labels(per, self.max_boxes, device='cpu')
         bref, cref = meta.add(boxes.numpy()), meta.add(counts.numpy())
         pref = plref = rref = None
+        if any(f.get('cloud') is not None for f in frames):
+            return self._cloud_batch(frames, indices, rng, meta, arena, la, iref, mid_bytes, lref, lut, bref, cref)
         if any(f.get('points') is not None for f in frames):
             pts, plab, _ = sample_points([f.get('points', ()) for f in frames], [f.get('point_labels') for f in frames], self.num_points, indices, rng)
             pref, plref = meta.add(pts), meta.add(plab)
@@ -387,3 +520,24 @@ class TrainBatcher:
         points = _normalize_points(meta.tensor(pref), self.point_dtype) if pref is not None else None
         return Batch(images, meta.tensor(rref) if rref is not None else None, points, meta.tensor(bref), meta.tensor(cref), png, png_w,
                      meta.tensor(plref) if plref is not None else None)
+
+    def _cloud_batch(self, frames, indices, rng, meta, arena, la, iref, mid_bytes, lref, lut, bref, cref):
+        R, B = self.R, len(frames)
+        if any(f.get('cloud') is None for f in frames) or any(f.get(k) is not None for f in frames for k in ('radar', 'points', 'point_labels')):
+            raise ValueError("TrainBatcher: every frame carries a `cloud`, or none does; a `cloud` replaces `radar`, `points` and `point_labels`")
+        cols = [dict(f.get('cloud_columns') or {}) for f in frames]
+        if any(c != cols[0] for c in cols) or set(cols[0]) - {'map', 'points', 'label'} or ('label' in cols[0] and 'points' not in cols[0]):
+            raise ValueError("TrainBatcher: `cloud_columns` is one dict for all frames with 'map', optionally 'points' and with it 'label'")
+        packed = pack_clouds([f['cloud'] for f in frames], self.device)
+        cref_ = _plan_clouds(meta, packed, cols[0].get('map', MAP_COLUMNS))
+        xref = None
+        if 'points' in cols[0]:
+            xref = meta.add(draw_indices([f[1] for f in packed.frames], self.num_points, indices, rng))
+        meta.commit()
+        images = _launch_images(meta, arena, iref, mid_bytes, lut, R, self.dtype)
+        png, png_w = _launch_labels(meta, la.data, lref, B, R, self.num_classes_seg, self.label_dtype)
+        radar = _launch_radar_maps(meta, packed, cref_, R, self.cell, False, torch.float32)
+        points = pc_labels = None
+        if xref is not None:
+            points, pc_labels = _launch_radar_points(meta, packed, cref_, xref, cols[0]['points'], cols[0].get('label'), self.num_points, self.point_dtype)
+        return Batch(images, radar, points, meta.tensor(bref), meta.tensor(cref), png, png_w, pc_labels)

@@ -8,6 +8,7 @@
     seg_maps_frames(se, lane, shapes, arena)         achelous.py:283-345    -> per-frame views   both class maps + the overlay image, ragged batch, one launch
     correct_boxes_frames(rows, cnt, (R, R), shapes)  utils_bbox.py:5-30     -> [B,max_det,7]     every frame's own (H, W)
     detect_frames(net, frames, radar, points)        achelous.py:190-345    camera bytes of B frames of different sizes -> boxes, class maps, overlays
+    detect_frames_from_clouds(net, frames, clouds)   + radar_feature_map_generate.ipynb   the same from raw radar point clouds (data.radar_maps_batch / radar_points_batch)
 HIP kernels through the C ABI; no CPU fallback.
 """
 import contextlib
@@ -374,10 +375,16 @@ def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4
     R = net.resolution
     arena = _data._as_arena(frames, 3, radar_maps.device, 'images')
     B = len(arena.frames)
-    shapes = [(f[1], f[2]) for f in arena.frames]
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = preprocess_input_radar(radar_maps, dtype)
     xp = normalize_points(points, dtype)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness)
+
+
+def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness):
+    """`detect_frames` from the three prepared network inputs on"""
+    R, B = net.resolution, len(arena.frames)
+    shapes = [(f[1], f[2]) for f in arena.frames]
     (det, se, lane, pc), (rows, idx, cnt) = net.forward_detect(x, xr, xp, conf_thres, nms_thres, max_det)
     boxes = correct_boxes_frames(rows, cnt, (R, R), shapes, letterbox_image)
     maps = seg_maps_frames(se, lane, shapes, arena if overlay else None, palette_se, palette_line, keep_classes, blend, brightness,
@@ -386,3 +393,24 @@ def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4
     if overlay:
         res['overlay'] = maps['overlay']
     return res
+
+
+def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_points=512, columns=None, point_columns=None, cell=None, conf_thres=0.5, nms_thres=0.4,
+                              letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE,
+                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda'):
+    """`detect_frames` from raw radar point clouds instead of ready radar maps and sampled points: `clouds` is a list of CPU float32 / float64 arrays [n_i, F] (or
+    `data.Clouds` already on the device), uploaded once.  The normalised radar map is `data.radar_maps_batch(..., normalize=True)` (the reference's offline
+    rasterisation, then its min-max scaling: `columns` = the columns of range, doppler, rcs, u, v, default 0..4; `cell` default (6.0, 3.375)); the points are
+    `data.radar_points_batch`: `num_points` rows per frame by `indices` [B, N] or drawn from `rng`, the columns `point_columns` (default: the first
+    `net.pc_channels`), normalised.  Two launches for the map and one for the points whatever B is, nothing read back; everything else and the result as `detect_frames`."""
+    from . import data as _data
+    R = net.resolution
+    packed = _data._as_clouds(clouds, device)
+    arena = _data._as_arena(frames, 3, packed.data.device, 'images')
+    B = len(arena.frames)
+    if len(packed.frames) != B:
+        raise ValueError(f"detect_frames_from_clouds: one cloud per frame expected, got {len(packed.frames)} for {B} frames")
+    x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
+    xr = _data.radar_maps_batch(packed, R, _data.MAP_COLUMNS if columns is None else columns, _data.CELL if cell is None else cell, True, dtype)
+    xp, _ = _data.radar_points_batch(packed, tuple(range(net.pc_channels)) if point_columns is None else point_columns, None, num_points, indices, rng, dtype)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness)

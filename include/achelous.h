@@ -449,6 +449,30 @@ int ach_data_labels_batch(const uint8_t* arena, int64_t arena_bytes, const int64
                           const int32_t* tabs_dev, int64_t tabs_len, int32_t B, int32_t R, int32_t num_classes_seg, void* png, void* png_w, int32_t label_kind,
                           void* stream);
 
+/* Both radar inputs of the network from raw radar point clouds (achelous_amd/csrc/k_radarmap.h; achelous_amd/data.py): the reference's offline map generation
+ * (radar_feature_map_generate.ipynb) and its per-frame point sampling (utils/dataloader.py:137-141) for a whole batch of ragged clouds, with a launch count that
+ * does not depend on the batch and no device-to-host copy.  All clouds sit in one packed arena of fp32 (in_kind 0) or fp64 (in_kind 1) rows, aligned to its
+ * element size, `arena_elems` elements long; frames are described by a host-built int64 table of 16 columns per frame whose copy on the device the kernels read.
+ * Cloud table: 0 element offset of the first row, 1 n (rows), 2 F (columns per row), 3 row stride in elements (>= F), 4 / 5 / 6 the columns of range, doppler
+ * and RCS (the map's three channels), 7 / 8 the columns of u and v, 9-15 unused.  Both entries read the HOST copy first and check every extent against the
+ * arena and every column against F (ach_data_radar_points also every row index against n): a bad table returns ACH_ERR_INVALID with a message and launches
+ * nothing.  The kernels test every cell index computed from the data on the device.
+ *   ach_data_radar_maps   `raw` [B, 3, R, R] fp32: per channel and point in row order, x = int(u / cell_u), y = int(v / cell_v) in float64 (truncation toward
+ *                       zero; an index in [-R, -1] wraps, anything else outside, NaN and infinities skip the point); if raw[ch][y][x] != 0 and the un-wrapped
+ *                       x >= 1 then x -= 1; raw[ch][y][x] = the channel's value rounded once to fp32.  n = 0 gives a zero map; n is not limited.  One launch.
+ *                       `out` not NULL: also (raw - min) / (max - min) + 1e-13 with min / max per frame over all channels, as ach_preprocess_radar computes it
+ *                       from `raw` (the same bits), [B, 3, R, R] of out_kind 0 / 1 / 2 = fp32 / bf16 / fp16; the extrema come out of the first launch through
+ *                       `partial` (at least 2 * B * R floats are always enough), so this is one more launch.  R <= 2048, else ACH_ERR_UNSUPPORTED.
+ *   ach_data_radar_points N rows per frame by `indices` [B, N] int64 (host and device copies), the D <= 16 columns `columns` (host int32) each divided by its L2
+ *                       norm over the sampled rows in fp32 (sklearn normalize(axis=0); a zero column stays zero) -> `points` [B, D, N] of out_kind 0 / 1 / 2;
+ *                       label_column >= 0: that column of the sampled rows -> `labels` [B, N] int64 (label_column < 0 and labels NULL: none).  Every cloud
+ *                       holds at least one row.  One launch. */
+int ach_data_radar_maps(const void* arena, int64_t arena_elems, int32_t in_kind, const int64_t* table_host, const int64_t* table_dev, int32_t B, int32_t R,
+                        double cell_u, double cell_v, float* raw, float* partial, int64_t partial_floats, void* out, int32_t out_kind, void* stream);
+int ach_data_radar_points(const void* arena, int64_t arena_elems, int32_t in_kind, const int64_t* table_host, const int64_t* table_dev, const int64_t* indices_host,
+                          const int64_t* indices_dev, const int32_t* columns, int32_t D, int32_t label_column, int32_t B, int32_t N, void* points,
+                          int32_t out_kind, int64_t* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
