@@ -83,82 +83,12 @@ int ach_load_weights(ach_handle* h, const ach_tensor_desc* tensors, size_t n) {
     return guarded(h, [&] { h->eng->load(tensors, n); });
 }
 
-int ach_set_option(ach_handle* h, const char* key, int32_t value) {
-    return guarded(h, [&] {
-        if (!key) throw ach::AchError{ACH_ERR_INVALID, "null option"};
-        if (std::string(key) == "full_taps") h->eng->full_taps = value != 0;
-        else if (std::string(key) == "streams") h->eng->multi_stream = value != 0;
-        else if (std::string(key) == "graph") h->eng->use_graph = value != 0;
-        else if (std::string(key) == "fused_mlp") h->eng->fuse_mlp = value != 0;
-        else if (std::string(key) == "mlp_split") h->eng->mlp_split = value;
-        else if (std::string(key) == "row_conv") h->eng->row_conv = value != 0;
-        else if (std::string(key) == "fused_rc") h->eng->fuse_rc = value != 0;
-        else if (std::string(key) == "dw_tile") h->eng->dw_tile = value != 0;
-        else if (std::string(key) == "stem_mfma") h->eng->stem_mfma = value != 0;
-        else if (std::string(key) == "point_stream2") h->eng->point_on_head_stream = value;
-        else if (std::string(key) == "head_batch") h->eng->head_batch = value != 0;
-        else if (std::string(key) == "head_fuse") h->eng->head_fuse = value != 0;
-        else if (std::string(key) == "head_fuse_dbg") h->eng->head_fuse_dbg = value;
-        else if (std::string(key) == "side_priority") h->eng->side_low_priority = value;
-        else if (std::string(key) == "head_lds_pad") h->eng->head_lds_pad = value < 0 ? 0 : (value > 65536 ? 65536 : value);
-        else if (std::string(key) == "head_stream") h->eng->head_stream = value != 0;
-        else if (std::string(key) == "split_decoders") h->eng->split_decoders = value;
-        else if (std::string(key) == "group_wpc") h->eng->group_wpc = value < 0 ? 0 : value;
-        else if (std::string(key) == "group_max") h->eng->group_max = value < 0 ? 0 : value;
-        else if (std::string(key) == "dec_fork") h->eng->dec_fork = value < 0 ? 0 : (value > 3 ? 3 : value);
-        else if (std::string(key) == "radar_start") h->eng->radar_start = value;
-        else if (std::string(key) == "pipeline") h->eng->pipeline = value != 0;
-        else if (std::string(key) == "pool_strip") h->eng->pool_strip = value;
-        else if (std::string(key) == "fused_mv2") h->eng->fuse_mv2 = value != 0;
-        else if (std::string(key) == "dw_even") h->eng->dw_even = value != 0;
-        else if (std::string(key) == "xca_mfma") h->eng->xca_mfma = value != 0;
-        else if (std::string(key) == "xca_frame") h->eng->xca_frame = value;
-        else if (std::string(key) == "xca_fold_mfma") h->eng->xca_fold_mfma = value != 0;
-        else if (std::string(key) == "xca_slice") h->eng->xca_slice = value;
-        else if (std::string(key) == "xca_front_waves") h->eng->xca_front_waves = value;
-        else if (std::string(key) == "xca_back_waves") h->eng->xca_back_waves = value;
-        else if (std::string(key) == "gemm_rows") h->eng->gemm_rows = (value == 2 || value == 4) ? value : 1;
-        else if (std::string(key) == "radar_rows4") h->eng->radar_rows4 = value;
-        else if (std::string(key) == "radar_skip") h->eng->radar_skip = value != 0;
-        else if (std::string(key) == "radar_bg") h->eng->radar_bg = value != 0;
-        else if (std::string(key) == "radar_pool_sparse") h->eng->radar_pool_sparse = value != 0;
-        else if (std::string(key) == "radar_compact") h->eng->radar_compact = value != 0;
-        else if (std::string(key) == "head_mfma") h->eng->head_mfma = value != 0;
-        else if (std::string(key) == "head_rows") h->eng->head_rows = value;
-        else if (std::string(key) == "xwait2_op") h->eng->dbg_xwait2_op = value;
-        else if (std::string(key) == "gemm_blocks") h->eng->gemm_blocks = value;
-        else if (std::string(key) == "sdta_fuse") h->eng->sdta_fuse = value;
-        else if (std::string(key) == "level_chain") h->eng->level_chain = value != 0;
-        else if (std::string(key) == "level_rows") h->eng->level_rows = value != 0;
-        else if (std::string(key) == "mlp_band") h->eng->mlp_band = value;
-        else if (std::string(key) == "mlp_band_run") h->eng->mlp_band_run = value != 0;
-        else if (std::string(key) == "mlp_band_dbg") h->eng->mlp_band_dbg = value;
-        else if (std::string(key) == "mlp_band_lean") h->eng->mlp_band_lean = value;
-        else if (std::string(key) == "head_band") h->eng->head_band = value > 0 ? value : 40;
-        else if (std::string(key) == "head_grid") h->eng->head_grid = value;
-        else if (std::string(key) == "head_debug") h->eng->head_debug = value;
-        else if (std::string(key) == "attn_mfma") h->eng->attn_mfma = value != 0;
-        else if (std::string(key) == "ds_fuse") h->eng->ds_fuse = value != 0;
-        else if (std::string(key) == "sa_fuse") h->eng->sa_fuse = value != 0;
-        else if (std::string(key) == "pn2_fps_all") h->eng->pn2_fps_all = value != 0;
-        else if (std::string(key) == "ghost_rb") h->eng->ghost_rb = value > 0 ? value : 5;
-        else if (std::string(key) == "pc_chain") h->eng->pc_chain = value != 0;
-        else if (std::string(key) == "mlp_split_hw") h->eng->mlp_split_hw = value;
-        else if (std::string(key) == "radar_direct") h->eng->radar_direct = value != 0;
-        else if (std::string(key) == "mv_stem") h->eng->mv_stem = value != 0;
-        else if (std::string(key) == "csp_fuse") h->eng->csp_fuse = value < 0 ? 0 : (value > 2 ? 2 : value);
-        else if (std::string(key) == "band_rows_s3") h->eng->band_rows_s3 = value;
-        else if (std::string(key) == "spp_split") h->eng->spp_split = value;
-        else if (std::string(key) == "ffn_rows2") h->eng->ffn_rows2 = value != 0;
-        else if (std::string(key) == "csp_band") h->eng->csp_band = value > 0 ? value : 40;
-        else if (std::string(key) == "ghost_fuse") h->eng->ghost_fuse = value != 0;
-        else if (std::string(key) == "io_bf16") {
-            if (value != 0 && h->eng->cfg.dtype != ACH_DTYPE_F16) throw ach::AchError{ACH_ERR_INVALID, "io_bf16 applies to the fp16-storage engine (ACH_DTYPE_F16) only"};
-            h->eng->io_bf16 = value != 0;
-        }
-        else throw ach::AchError{ACH_ERR_INVALID, std::string("unknown option: ") + key};
-    });
+// options: lookups in the table of engine_options.h (engine.cpp).  ach_get_option reads the engine only; a failure still sets the handle's last error.
+int ach_set_option(ach_handle* h, const char* key, int32_t value) { return guarded(h, [&] { h->eng->set_option(key, value); }); }
+int ach_get_option(const ach_handle* h, const char* key, int32_t* value) {
+    return guarded(const_cast<ach_handle*>(h), [&] { if (!value) throw ach::AchError{ACH_ERR_INVALID, "null option value"}; *value = h->eng->get_option(key); });
 }
+const char* ach_option_key(int32_t index) { return ach::EngineBase::option_key(index); }
 
 int ach_plan(ach_handle* h, int32_t batch) {
     return guarded(h, [&] { h->eng->plan(batch); });

@@ -41,13 +41,14 @@ EngineBase::~EngineBase() {
         for (int k = 0; k < kSideStreams; ++k) (void)hipEventDestroy(ev_end[k]);          // (the streams belong to the process-wide pool)
         (void)hipEventDestroy(ev_fork);
         for (int k = 0; k < kJoinEvents; ++k) (void)hipEventDestroy(ev_join[k]);
-        for (int q = 0; q < 2; ++q) { (void)hipEventDestroy(ev_x[q]); (void)hipEventDestroy(ev_x2[q]); (void)hipEventDestroy(ev_x3[q]); for (int k = 0; k < kSideStreams; ++k) (void)hipEventDestroy(ev_done[k][q]); }
+        for (int q = 0; q < 2; ++q) { for (auto& x : xdep) (void)hipEventDestroy(x.ev[q]); for (int k = 0; k < kSideStreams; ++k) (void)hipEventDestroy(ev_done[k][q]); }
     }
     for (auto& pr : probes) { for (auto e : pr.ev0) (void)hipEventDestroy(e); for (auto e : pr.ev1) (void)hipEventDestroy(e); }
 }
 
 void EngineBase::load(const ach_tensor_desc* t, size_t n) {
     (void)hipDeviceSynchronize();          // a forward in flight still reads the packed weights the next plan() will overwrite
+    invalidate_plan();                     // the plan holds the OLD weights, folded and packed: ach_plan must follow
     weights.clear();
     for (size_t i = 0; i < n; ++i) {
         if (!t[i].name || !t[i].data || t[i].ndim < 0 || t[i].ndim > 4) throw AchError{ACH_ERR_INVALID, "bad tensor descriptor"};
@@ -97,14 +98,48 @@ void* EngineBase::up_raw(const void* src, size_t bytes) {
     if (!measuring) ACH_HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
     return d;
 }
-void EngineBase::reset_plan() {
+void EngineBase::invalidate_plan() {
 #if !defined(ACH_HOSTEMU)
+    if (!graphs.empty()) (void)hipDeviceSynchronize();       // a replay may still be running
     drop_graphs();
 #endif
     for (auto& pr : probes) pr.first = pr.last = -1;
-    cur_stream = 0; pending_wait = -1; pending_wait2 = -1;
-    ops.clear(); taps.clear(); tap_order.clear(); t_regions.clear(); sat_dev_regions = 0;
+    ops.clear(); taps.clear(); tap_order.clear(); batch = 0;
+}
+void EngineBase::reset_plan(int B) {
+    invalidate_plan(); batch = B;
+    cur_stream = 0; pending_wait = -1; pending_wait2 = -1; pending_xwait = 0;
+    t_regions.clear(); sat_dev_regions = 0;
     warena_used = 0; aarena_used = 0;
+}
+
+// ---- options: the table of engine_options.h
+enum class OptionRule { Bool, Int, Clamp, Positive, GemmRows, IoBf16 };
+struct OptionDef { const char* key; int (*get)(const EngineBase&); void (*set)(EngineBase&, int); int def; OptionRule rule; int lo, hi; };
+static const OptionDef kOptions[] = {
+#define ACH_OPTION(key, type, member, def, rule, lo, hi) {key, [](const EngineBase& e) { return int(e.member); }, [](EngineBase& e, int v) { e.member = type(v); }, def, OptionRule::rule, lo, hi},
+#include "engine_options.h"
+#undef ACH_OPTION
+};
+static const OptionDef& find_option(const char* key) {
+    if (!key) throw AchError{ACH_ERR_INVALID, "null option"};
+    for (const OptionDef& o : kOptions) if (std::strcmp(o.key, key) == 0) return o;
+    throw AchError{ACH_ERR_INVALID, std::string("unknown option: ") + key};
+}
+const char* EngineBase::option_key(int index) { return (index >= 0 && size_t(index) < sizeof(kOptions) / sizeof(kOptions[0])) ? kOptions[index].key : nullptr; }
+int EngineBase::get_option(const char* key) const { return find_option(key).get(*this); }
+void EngineBase::set_option(const char* key, int value) {
+    const OptionDef& o = find_option(key);
+    if (o.rule == OptionRule::IoBf16 && value != 0 && cfg.dtype != ACH_DTYPE_F16) throw AchError{ACH_ERR_INVALID, "io_bf16 applies to the fp16-storage engine (ACH_DTYPE_F16) only"};
+    switch (o.rule) {
+        case OptionRule::Int: break;
+        case OptionRule::Bool: case OptionRule::IoBf16: value = value != 0; break;
+        case OptionRule::Clamp: value = value < o.lo ? o.lo : (value > o.hi ? o.hi : value); break;
+        case OptionRule::Positive: value = value > 0 ? value : o.def; break;
+        case OptionRule::GemmRows: value = (value == 2 || value == 4) ? value : 1; break;
+    }
+    o.set(*this, value);
+    invalidate_plan();            // the plan was built from the old value (and run_eager reads some options live)
 }
 // Side streams are shared by every engine of the process on a device (one set per priority pattern) and live as long as the process:
 // the runtime maps streams onto a handful of hardware queues, and a process with more than four ACTIVE streams loses a quarter of its
@@ -138,9 +173,7 @@ void EngineBase::ensure_streams() {
     ACH_HIP_CHECK(hipEventCreate(&ev_fork));
     for (int k = 0; k < kJoinEvents; ++k) ACH_HIP_CHECK(hipEventCreate(&ev_join[k]));
     for (int q = 0; q < 2; ++q) {
-        ACH_HIP_CHECK(hipEventCreate(&ev_x[q]));
-        ACH_HIP_CHECK(hipEventCreate(&ev_x2[q]));
-        ACH_HIP_CHECK(hipEventCreate(&ev_x3[q]));
+        for (auto& x : xdep) ACH_HIP_CHECK(hipEventCreate(&x.ev[q]));
         for (int k = 0; k < kSideStreams; ++k) ACH_HIP_CHECK(hipEventCreate(&ev_done[k][q]));
     }
     streams_ready = true;
@@ -185,16 +218,16 @@ void EngineBase::run_eager(hipStream_t s) {
         if (multi && op.stream > 0) { st = side_stream[op.stream - 1]; used[op.stream - 1] = true; }
         if (multi && op.wait_ev >= 0) (void)hipStreamWaitEvent(st, ev_join[op.wait_ev], 0);
         if (multi && op.wait_ev2 >= 0) (void)hipStreamWaitEvent(st, ev_join[op.wait_ev2], 0);
-        if (piped && op.xwait && issued > 0) (void)hipStreamWaitEvent(st, ev_x[par ^ 1], 0);
-        if (piped && (dbg_xwait2_op >= 0 ? int(i) == dbg_xwait2_op : op.xwait2) && issued > 0 && x2_recorded[par ^ 1]) (void)hipStreamWaitEvent(st, ev_x2[par ^ 1], 0);
-        if (piped && op.xwait3 && issued > 0 && x3_recorded[par ^ 1]) (void)hipStreamWaitEvent(st, ev_x3[par ^ 1], 0);
+        if (piped && issued > 0) {
+            unsigned w = op.xwait;
+            if (dbg_xwait2_op >= 0) w = (w & ~(1u << kXDecoders)) | (int(i) == dbg_xwait2_op ? 1u << kXDecoders : 0u);
+            for (int d = 0; w; ++d, w >>= 1) if ((w & 1) && xdep[d].recorded[par ^ 1]) (void)hipStreamWaitEvent(st, xdep[d].ev[par ^ 1], 0);
+        }
         for (auto& pr : probes) if (int(i) == pr.first) (void)hipEventRecord(pr.ev0[size_t(pr.count % kProbeEvents)], st);
         op.fn(st);
         for (auto& pr : probes) if (int(i) == pr.last) { (void)hipEventRecord(pr.ev1[size_t(pr.count % kProbeEvents)], st); ++pr.count; }
         if (multi && op.signal_ev >= 0) (void)hipEventRecord(ev_join[op.signal_ev], st);
-        if (piped && op.xsignal) (void)hipEventRecord(ev_x[par], st);
-        if (piped && op.xsignal2) { (void)hipEventRecord(ev_x2[par], st); x2_recorded[par] = true; }
-        if (piped && op.xsignal3) { (void)hipEventRecord(ev_x3[par], st); x3_recorded[par] = true; }
+        if (piped) for (unsigned d = 0, g = op.xsignal; g; ++d, g >>= 1) if (g & 1) { (void)hipEventRecord(xdep[d].ev[par], st); xdep[d].recorded[par] = true; }
     }
     if (detect_tail) detect_tail((multi && detect_stream > 0 && used[detect_stream - 1]) ? side_stream[detect_stream - 1] : s);   // det maps are final on that stream
     if (piped) {

@@ -147,7 +147,7 @@ __device__ __forceinline__ void xca_gemm_units(const GemmParams& g, int b, int t
 
 // ---- ONE launch, one workgroup per frame.  MEASURED SLOWER than the four launches it replaces (EN-S0, batch 64: 121 / 85 / 96 us against 64 / 56 / 70 us isolated,
 // 40.4 k against 41.6 k frames/s, profiles/r06_xca/): every phase is a chain of L2 round trips and 16 waves per frame cannot overlap them.  Kept as option xca_frame = 1
-// (the correct statement of the experiment, and the batch-1 form); the default is the two-launch form below.
+// (the correct statement of the experiment, and the batch-1 form); the default is the four-launch form with the xca_fold_mfma finalize launch above (xca_frame = 0).
 template <class T, int XCA_DMAX, int AFL, int PEL, int NWV>
 __global__ __launch_bounds__(64 * NWV) void xca_frame_kernel(const XcaFrameParams p) { f16_sat_mode<T>();
     using L = XcaFrameLds<T, XCA_DMAX, AFL, PEL>;
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(64 * NWV) void xca_frame_kernel(const XcaFrameParam
     xca_gemm_units<T, NWV>(p.proj, b, 0, ntt, p.N);
 }
 
-// ---- TWO launches (option xca_frame = 2, the default of the 16-bit engines):
+// ---- TWO launches (option xca_frame = 2; not the default: the 16-bit engines run the four-launch form with xca_fold_mfma, xca_frame = 0):
 //   xca_front_kernel, workgroup = (frame, slice of `per` tokens): qkv of the slice, then the slice's partial Gram sums — what the qkv GEMM and the Gram launch did, the
 //                     slice's q and k read back by the compute unit that wrote them;
 //   xca_back_kernel,  workgroup = (frame, block of 64 tokens): sum of the partials + softmax + fold (every workgroup of a frame computes the SAME Weff and writes the

@@ -36,7 +36,7 @@ class NativeLibrary:
     SYMBOLS = ('ach_create', 'ach_destroy', 'ach_last_error', 'ach_load_weights', 'ach_plan', 'ach_arena_bytes',
                'ach_forward', 'ach_forward_detect', 'ach_join', 'ach_forwards_in_flight', 'ach_decode', 'ach_nms_workspace_bytes', 'ach_nms', 'ach_tap_count', 'ach_tap_name',
                'ach_tap_shape', 'ach_read_tap', 'ach_plan_launches', 'ach_op_name', 'ach_op_bytes', 'ach_op_layout_bytes', 'ach_op_flops', 'ach_op_stream',
-               'ach_forward_profiled', 'ach_set_probe', 'ach_read_probe', 'ach_set_probe_range', 'ach_read_probe_slot', 'ach_bench_gemm', 'ach_set_option', 'ach_preprocess_radar',
+               'ach_forward_profiled', 'ach_set_probe', 'ach_read_probe', 'ach_set_probe_range', 'ach_read_probe_slot', 'ach_bench_gemm', 'ach_set_option', 'ach_get_option', 'ach_option_key', 'ach_preprocess_radar',
                'ach_normalize_points', 'ach_preprocess_image', 'ach_seg_argmax', 'ach_seg_resize_argmax', 'ach_correct_boxes', 'ach_train_pn2_fps', 'ach_train_pn2_group', 'ach_train_pn2_group_bwd', 'ach_train_pn2_interp', 'ach_train_gemm', 'ach_train_gemm_p', 'ach_train_set_gemm_precision', 'ach_train_get_gemm_precision', 'ach_train_bn_stats', 'ach_train_bn_running', 'ach_train_bn_relu_fwd', 'ach_train_bn_relu_bwd', 'ach_train_dw3x3', 'ach_train_dw3x3_wgrad', 'ach_train_max_points', 'ach_train_log_softmax', 'ach_resample_pass_u8', 'ach_train_act', 'ach_train_mul', 'ach_train_layernorm', 'ach_train_layernorm_bwd', 'ach_train_dwconv', 'ach_train_dwconv_wgrad',
                'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
                'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
@@ -60,6 +60,14 @@ class NativeLibrary:
         L.ach_load_weights.restype = ctypes.c_int
         L.ach_set_option.argtypes = [vp, ctypes.c_char_p, i32]
         L.ach_set_option.restype = ctypes.c_int
+        # (the two option queries are bound where the library exports them: the co-residency tests also load tests/variants libraries that were built
+        #  before these entries existed; tests/test_abi_and_host.py holds the product to every declared symbol, and get_option on a library without them raises)
+        if hasattr(L, 'ach_get_option'):
+            L.ach_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
+            L.ach_get_option.restype = ctypes.c_int
+        if hasattr(L, 'ach_option_key'):
+            L.ach_option_key.argtypes = [i32]
+            L.ach_option_key.restype = ctypes.c_char_p
         L.ach_plan.argtypes = [vp, i32]
         L.ach_plan.restype = ctypes.c_int
         L.ach_arena_bytes.argtypes = [vp]
@@ -252,7 +260,7 @@ class NativeEngine:
 
     # ---------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
-        """Reference-keyed state_dict (achelous.py:171) -> folded + packed device weights."""
+        """Reference-keyed state_dict (achelous.py:171) -> the handle's host copy of the weights; plan() folds and packs them on the device."""
         keep, descs = [], []
         for k, v in state_dict.items():
             if not torch.is_floating_point(v):
@@ -276,6 +284,12 @@ class NativeEngine:
         self.batch = 0
         if key == 'io_bf16' and self.dtype == DTYPE_F16:
             self.torch_dtype = torch.bfloat16 if int(value) else torch.float16
+
+    def get_option(self, key):
+        """the stored (normalised) value of an option"""
+        v = ctypes.c_int32()
+        self._check(self.L.ach_get_option(self.h, key.encode(), ctypes.byref(v)))
+        return int(v.value)
 
     def plan(self, batch):
         self._check(self.L.ach_plan(self.h, int(batch)))

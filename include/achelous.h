@@ -88,64 +88,90 @@ int ach_create(const ach_config* cfg, ach_handle** out);
 void ach_destroy(ach_handle* h);
 const char* ach_last_error(const ach_handle* h);
 
-/* Copies, folds (eval-mode BatchNorm, LayerNorm affine, layer scale, constant positional encoding) and repacks
- * the weights into kernel-native layouts on the device.  Integer buffers (num_batches_tracked) may be omitted. */
+/* Copies the weights to the host side of the handle.  Folding (eval-mode BatchNorm, LayerNorm affine, layer scale, constant positional
+ * encoding) and repacking into kernel-native layouts on the device happen in ach_plan, which must follow: loading drops the handle's plan,
+ * and ach_forward returns ACH_ERR_INVALID until ach_plan has run again.  Integer buffers (num_batches_tracked) may be omitted. */
 int ach_load_weights(ach_handle* h, const ach_tensor_desc* tensors, size_t n);
 
-/* Options, set before ach_plan.  "full_taps" = 1: also write to HBM the SURVEY §8(a) boundaries that production plans keep
- * on-chip (the 32-channel full-resolution decoder tensors), so that parity tests can read them back.
- * "streams" = 0: launch everything on the caller's stream (default 1: the independent radar and point branches run on two
- * engine-owned side streams, forked from / joined into the caller's stream with events).
- * "graph" = 1: capture the plan into a hipGraph per distinct set of I/O pointers and replay it (default 0: measured no faster
- * than the interleaved eager launches on the side streams).
- * Kernel-selection switches, all default 1, kept so that each fused kernel can be A/B-measured against the layer-wise path it
- * replaced (results agree to rounding): "fused_mlp" (EdgeNeXt blocks and decoder conv pairs through k_mlp.h), "mlp_split"
- * (-1 auto / 0 / 1: four waves per pixel tile in k_mlp.h), "row_conv" (offset/modulator convs through k_conv3.h),
- * "split_decoders" (semantic decoder on its own stream), "fused_rc" (RCBlock conv + deformable sampling + contraction as one
- * kernel), "dw_tile" (LDS-tiled depthwise kernel on 10x10 maps), "head_batch" (detection-head layers batched over the levels),
- * "head_stream" (1: radar + point branches share low-priority stream 1, fusion + head + NMS run on stream 2 at the caller's priority; default 0: they queue behind the radar branch on stream 1),
- * "side_priority" (with head_stream = 0: bit mask of the side streams created at the lowest stream priority),
- * "point_stream2" (-1 auto / 0 / 1: the point branch opens stream 2 ahead of fusion + head; auto = PointNet++ only),
- * "stem_mfma" (the 4x4/s4 stem conv as an MFMA GEMM gathered from the NCHW image; 0: scalar-FMA kernel),
- * "radar_skip" (closed-form shortcut for empty 16-pixel segments of the first RCBlock, bit-identical), "radar_rows4" (0 / 1 / 2: a
- * workgroup owns four rows in the first / in all fused RCBlocks and the row-walking conv), "radar_start" (the radar branch is released
- * after backbone stage k = 0..3, -1 = at once; default -2 = stage 2 in the pipelined plan, stage 1 in the plain plan), "dw_even" (even deal of depthwise tap rows over the four SPLIT waves, d = 144), "xca_mfma" (XCA Gram
- * matrices on the matrix cores; 0: VALU kernel), "head_mfma" (default 0: bilinear phase of the fused segmentation head on MFMA —
- * measured slower), "gemm_rows" (default 1: 16-row sub-tiles per wave for GEMMs with K >= 1024 — 2 / 4 measured slower), "gemm_blocks" (workgroups a GEMM
- * launch aims for when its rows alone cannot fill the chip; 0 = 1024),
- * round 4: "io_bf16" (ACH_DTYPE_F16 only: the caller's input / output tensors are bf16, converted in the first / last kernels);
- * "ghost_fuse" (default 1: the neck's Ghost bottlenecks, shortcuts, Upsample modules and the SPP block as band kernels — k_ghost.h; bit-identical), "ghost_rb" (rows
- * per band of those kernels, default 5), "ds_fuse" (default 1: the channels-first LayerNorm of a downsample layer inside its 2x2 / stride-2 conv), "sa_fuse" (default 0:
- * ShuffleAttention's coefficient launch folded into the apply launch — measured slower), "pn2_fps_all" (default 1: PointNet++'s four farthest-point samplings as one
- * launch), "pc_chain" (default 1: PointNet's conv3 + conv4 as one two-layer chain launch), "mv_stem" (default 1, 16-bit engines: MobileViT's conv1 gathered straight
- * from the NCHW image instead of an NHWC copy + implicit GEMM), "radar_direct" (default 1, 16-bit engines: the first RCBlock pools and adds its residual straight
- * from the NCHW radar map; bit-identical), "mlp_split_hw" (default 1024: maps of at most this many pixels run the fused blocks with four waves per 16-pixel tile);
- * round 3 (16-bit engines): "head_rows" (2: last decoder level + segmentation head as the row-walking two-columns-per-lane kernel, 1: one
- * column, 0: the LDS tile kernel), "head_band" (rows per workgroup band of that kernel, default 40), "mlp_band" (1: EdgeNeXt blocks of
- * the instantiated shapes — d = 96 / 144 on maps up to 20 wide, d = 176 up to 10 wide — as the band kernel, 2: also stages 0 / 1, 0: never), "head_fuse" (a detection-head layer's depthwise + pointwise convs of both
- * towers and all levels as one launch), "radar_compact" (first RCBlock: per-pixel activity, active pixels compacted into dense tiles;
- * bit-identical), "level_chain" (a decoder level's kernel also applies the next level's low-resolution conv pair; bit-identical),
- * "sdta_fuse" (1: an SDTA encoder's conv cascade + tail copy + positional encoding as one launch on maps up to 20 x 20, 2: every map,
- * 0: never; bit-identical), "level_rows" (default 0: decoder levels as row-walking kernels — measured slower);  debugging only:
- * "xwait2_op" (pipelined mode: the launch index that waits for the previous forward's decoders), "head_debug" / "mlp_band_dbg" /
- * "head_fuse_dbg" (phase-kill timing variants, WRONG results);
- * round 5 (16-bit engines): "csp_fuse" (CSP-Dual-FPN decoders — 2, default: the two 32-channel levels (160 x 160 and full resolution) as row-walking launches
- * (k_csphead.h), the last one with the segmentation head in it; 1: the last level + head only; 0: layer-wise), "csp_band" (rows per band of those launches, default
- * 40), "head_lds_pad" (default 0: bytes of unused dynamic LDS per workgroup of the Ghost-FPN row-walking head = an occupancy cap; every cap measured slower);
- * "ffn_rows2" (default 1: MobileViT's feed-forward layers on the large maps with two 16-row tiles per wave; bit-identical), "mlp_band_run" (default 0: a stage's
- * band-kernel ConvEncoder blocks as one persistent launch with per-frame barriers; bit-identical, measured no faster), "dec_fork" (pipelined plan: where the
- * segmentation decoders leave the caller's stream — 1, default: in front of the shared ShuffleAttention stage (+0.9 %), 0: behind it (round 3), 2: as soon as the
- * neck's p3 exists, 3: the whole neck on stream 2, ordered against the next forward's backbone by a third cross-forward event (EdgeNeXt plans; level with 1);
- * bit-identical), "group_max" (default 1024; 0 = never: PointNet++'s shared-MLP + max-over-the-ball layers with a wave per ball for layers of at least this many balls;
- * bit-identical), "group_wpc" (default 4096; 0 = never: PointNet++ grouping with a workgroup per centroid on levels with at most this many centroids; bit-identical), "point_stream2" = 3 (the point branch on a stream of its own — the process's fourth: measured -1 %, and it leaves no stream for a collective);
- * round 6 (16-bit engines): "xca_fold_mfma" (default 1: the XCA finalize launch folds softmax(attn) into the projection weights on the matrix cores, one workgroup per (frame, head);
- * 0: round 5's fp32 VALU fold), "xca_frame" (default 0: four launches per attention; 2: two launches — qkv + Gram partials per token slice, softmax + fold + projection per 64 tokens;
- * 1: one launch with a workgroup per frame; both measured slower) with "xca_slice", "xca_front_waves", "xca_back_waves"; "radar_pool_sparse" (default 1: the first
- * RCBlock's pool stores a pixel only where the pooled map is, or was after the previous forward, non-zero) and "radar_bg" (default 1: the block's output map keeps relu(bias) at every
- * unoccupied pixel; rc_front neither reads nor writes such pixels) — both bit-identical, both carry masks from one forward to the next inside the plan's arena;
- * "mlp_band_lean" (default 0: the d = 96 band kernel with a 16-bit halo tile, 98 KB of LDS: measured neutral);
- * "pipeline" (see ach_join).  DESIGN.md §4 and profiles/NOTES_r0*.md have the measurement behind every default. */
+/* Options, set before ach_plan: a successful ach_set_option drops the handle's plan (ach_forward returns ACH_ERR_INVALID until ach_plan has run again; ach_join and
+ * ach_forwards_in_flight keep working).  The value is normalised as stated per key and stored; ach_get_option returns the stored value (reads the handle only; a failure still
+ * sets its ach_last_error), ach_option_key(i) enumerates the keys in the order below (NULL past the end).  An unknown key is ACH_ERR_INVALID.  One line per key: values, default,
+ * what it selects.  The table itself, with the measurement behind every default, is achelous_amd/csrc/engine_options.h; DESIGN.md §4 and profiles/NOTES_r0*.md have the rest.
+ * "16-bit engines" = ACH_DTYPE_BF16 / ACH_DTYPE_F16.
+ * The plan and its schedule
+ *   "full_taps"         0 / 1, default 0: also write to HBM the SURVEY §8(a) boundaries that production plans keep on-chip (the 32-channel full-resolution decoder tensors), so that parity tests can read them back
+ *   "streams"           0 / 1, default 1: the independent radar and point branches run on two engine-owned side streams, forked from / joined into the caller's stream with events; 0: everything on the caller's stream
+ *   "graph"             0 / 1, default 0: capture the plan into a hipGraph per distinct set of I/O pointers and replay it (measured no faster than the interleaved eager launches on the side streams)
+ *   "io_bf16"           0 / 1, default 0 (round 4): ACH_DTYPE_F16 only, else ACH_ERR_INVALID — the caller's input / output tensors are bf16, converted in the first / last kernels
+ *   "pipeline"          0 / 1, default 0: consecutive forwards overlap (see ach_join)
+ *   "dec_fork"          0..3 (clamped), default 1 (round 5): pipelined plan, where the segmentation decoders leave the caller's stream — 1: in front of the shared ShuffleAttention stage (+0.9 %), 0: behind it (round 3), 2: as soon as the neck's p3 exists, 3: the whole neck on stream 2, ordered against the next forward's backbone by a third cross-forward event (EdgeNeXt plans; level with 1); bit-identical
+ *   "radar_start"       integer, default -2: the radar branch is released after backbone stage k = 0..3, -1 = at once; -2 = stage 2 in the pipelined plan, stage 1 in the plain plan
+ *   "head_stream"       0 / 1, default 0: 1 = radar + point branches share low-priority stream 1, fusion + head + NMS run on stream 2 at the caller's priority; 0: they queue behind the radar branch on stream 1
+ *   "side_priority"     bit mask, default 3: with head_stream = 0, the side streams created at the lowest stream priority
+ *   "point_stream2"     -1 / 0 / 1 / 3, default -1: the point branch opens stream 2 ahead of fusion + head (-1 auto = PointNet++ only); 3 (round 5) = a stream of its own — the process's fourth: measured -1 %, and it leaves no stream for a collective
+ *   "split_decoders"    integer, default 0: semantic decoder on its own stream (measured slower)
+ * Kernel selection, kept so that each fused kernel can be A/B-measured against the layer-wise path it replaced (results agree to rounding, or bit for bit where stated)
+ *   "fused_mlp"         0 / 1, default 1: EdgeNeXt blocks and decoder conv pairs through k_mlp.h
+ *   "mlp_split"         -1 / 0 / 1, default -1 (auto): four waves per pixel tile in k_mlp.h
+ *   "mlp_split_hw"      integer, default 1024: maps of at most this many pixels run the fused blocks with four waves per 16-pixel tile
+ *   "mlp_band"          0 / 1 / 2, default 1 (round 3, 16-bit engines): EdgeNeXt blocks of the instantiated shapes — d = 96 / 144 on maps up to 20 wide, d = 176 up to 10 wide — as the band kernel, 2: also stages 0 / 1, 0: never
+ *   "band_rows_s3"      integer, default 0 (= 5): rows per band of the stage-3 band kernel
+ *   "dw_even"           0 / 1, default 1: even deal of depthwise tap rows over the four SPLIT waves, d = 144
+ *   "dw_tile"           0 / 1, default 1: LDS-tiled depthwise kernel on 10x10 maps
+ *   "ds_fuse"           0 / 1, default 1 (round 4): the channels-first LayerNorm of a downsample layer inside its 2x2 / stride-2 conv
+ *   "sdta_fuse"         0 / 1 / 2, default 1 (round 3, 16-bit engines): an SDTA encoder's conv cascade + tail copy + positional encoding as one launch on maps up to 20 x 20, 2: every map, 0: never; bit-identical
+ *   "xca_mfma"          0 / 1, default 1: XCA Gram matrices on the matrix cores; 0: VALU kernel
+ *   "xca_fold_mfma"     0 / 1, default 1 (round 6, 16-bit engines): the XCA finalize launch folds softmax(attn) into the projection weights on the matrix cores, one workgroup per (frame, head); 0: round 5's fp32 VALU fold
+ *   "stem_mfma"         0 / 1, default 1: the 4x4/s4 stem conv as an MFMA GEMM gathered from the NCHW image; 0: scalar-FMA kernel
+ *   "mv_stem"           0 / 1, default 1 (round 4, 16-bit engines): MobileViT's conv1 gathered straight from the NCHW image instead of an NHWC copy + implicit GEMM
+ *   "fused_mv2"         0 / 1, default 1: MobileViT's MV2 blocks (1x1 -> dw3x3 -> 1x1) as one launch (k_mv2.h)
+ *   "attn_mfma"         0 / 1, default 1: MobileViT attention scores / P.V on MFMA (k_mvit.h) instead of one query per thread
+ *   "ffn_rows2"         0 / 1, default 1 (round 5, 16-bit engines): MobileViT's feed-forward layers on the large maps with two 16-row tiles per wave; bit-identical
+ *   "gemm_blocks"       integer, default 0 (= 1024): workgroups a GEMM launch aims for when its rows alone cannot fill the chip
+ *   "row_conv"          0 / 1, default 1: offset/modulator convs through k_conv3.h
+ *   "fused_rc"          0 / 1, default 1: RCBlock conv + deformable sampling + contraction as one kernel
+ *   "pool_strip"        integer, default 2: which RCBlock average pools use the 4-pixel strip kernel
+ *   "radar_skip"        0 / 1, default 1: closed-form shortcut for empty 16-pixel segments of the first RCBlock, bit-identical
+ *   "radar_rows4"       0 / 1 / 2, default 2: a workgroup owns four rows in the first / in all fused RCBlocks and the row-walking conv
+ *   "radar_compact"     0 / 1, default 1 (round 3, 16-bit engines): first RCBlock — per-pixel activity, active pixels compacted into dense tiles; bit-identical
+ *   "radar_direct"      0 / 1, default 1 (round 4, 16-bit engines): the first RCBlock pools and adds its residual straight from the NCHW radar map; bit-identical
+ *   "radar_bg"          0 / 1, default 1 (round 6, 16-bit engines): the first RCBlock's output map keeps relu(bias) at every unoccupied pixel; rc_front neither reads nor writes such pixels; bit-identical, carries masks from one forward to the next inside the plan's arena
+ *   "radar_pool_sparse" 0 / 1, default 1 (round 6, 16-bit engines): the first RCBlock's pool stores a pixel only where the pooled map is, or was after the previous forward, non-zero; bit-identical, carries masks from one forward to the next inside the plan's arena
+ *   "ghost_fuse"        0 / 1, default 1 (round 4): the neck's Ghost bottlenecks, shortcuts, Upsample modules and the SPP block as band kernels — k_ghost.h; bit-identical
+ *   "ghost_rb"          positive (else the default), default 5: rows per band of those kernels
+ *   "spp_split"         integer, default 0 (auto: 2): workgroups per frame of the fused SPP launch
+ *   "level_chain"       0 / 1, default 1 (round 3, 16-bit engines): a decoder level's kernel also applies the next level's low-resolution conv pair; bit-identical
+ *   "head_rows"         0 / 1 / 2, default 2 (round 3, 16-bit engines): last decoder level + segmentation head as the row-walking two-columns-per-lane kernel, 1: one column, 0: the LDS tile kernel
+ *   "head_band"         positive (else the default), default 40: rows per workgroup band of that kernel
+ *   "csp_fuse"          0..2 (clamped), default 2 (round 5, 16-bit engines): CSP-Dual-FPN decoders — 2: the two 32-channel levels (160 x 160 and full resolution) as row-walking launches (k_csphead.h), the last one with the segmentation head in it; 1: the last level + head only; 0: layer-wise
+ *   "csp_band"          positive (else the default), default 40: rows per band of those launches
+ *   "head_batch"        0 / 1, default 1: detection-head layers batched over the levels
+ *   "head_fuse"         0 / 1, default 1 (round 3, 16-bit engines): a detection-head layer's depthwise + pointwise convs of both towers and all levels as one launch
+ *   "pc_chain"          0 / 1, default 1 (round 4): PointNet's conv3 + conv4 as one two-layer chain launch
+ *   "pn2_fps_all"       0 / 1, default 1 (round 4): PointNet++'s four farthest-point samplings as one launch
+ *   "group_wpc"         >= 0 (negative = 0 = never), default 4096 (round 5): PointNet++ grouping with a workgroup per centroid on levels with at most this many centroids; bit-identical
+ *   "group_max"         >= 0 (negative = 0 = never), default 1024 (round 5): PointNet++'s shared-MLP + max-over-the-ball layers with a wave per ball for layers of at least this many balls; bit-identical
+ * Measured slower or level, kept
+ *   "gemm_rows"         1 / 2 / 4 (anything else = 1), default 1: 16-row sub-tiles per wave for GEMMs with K >= 1024 — 2 / 4 measured slower
+ *   "xca_frame"         0 / 1 / 2, default 0 (round 6, 16-bit engines): four launches per attention; 2: two launches — qkv + Gram partials per token slice, softmax + fold + projection per 64 tokens; 1: one launch with a workgroup per frame; both measured slower, DESIGN.md 4.5
+ *   "xca_slice"         integer, default 0 (64, 128 on maps of 1024 tokens or more): with xca_frame, tokens per workgroup of the front kernel
+ *   "xca_front_waves"   4 / 8 / 16, default 0 (by the number of work units): with xca_frame, waves per workgroup of the front kernel
+ *   "xca_back_waves"    4 / 8 / 16, default 0 (by the number of work units): with xca_frame, waves per workgroup of the back kernel
+ *   "sa_fuse"           0 / 1, default 0 (round 4): ShuffleAttention's coefficient launch folded into the apply launch — measured slower
+ *   "level_rows"        0 / 1, default 0 (round 3, 16-bit engines): decoder levels as row-walking kernels — measured slower
+ *   "head_mfma"         0 / 1, default 0: bilinear phase of the fused segmentation head on MFMA — measured slower
+ *   "head_grid"         integer, default 0 (= the kernel's own grid): persistent workgroups of the MFMA head kernel
+ *   "head_lds_pad"      0..65536 (clamped), default 0 (round 5): bytes of unused dynamic LDS per workgroup of the Ghost-FPN row-walking head = an occupancy cap; every cap measured slower
+ *   "mlp_band_run"      0 / 1, default 0 (round 5): a stage's band-kernel ConvEncoder blocks as one persistent launch with per-frame barriers; bit-identical, measured no faster
+ *   "mlp_band_lean"     integer, default 0 (round 6): the d = 96 band kernel with a 16-bit halo tile, 98 KB of LDS: measured neutral
+ * Debugging only
+ *   "xwait2_op"         launch index, default -1 (none): pipelined mode, the launch that waits for the previous forward's decoders instead of the planned one
+ *   "head_debug"        integer, default 0: phase-kill timing variant of the fused last decoder level, WRONG results
+ *   "mlp_band_dbg"      integer, default 0: phase-kill timing variant of the band kernel, WRONG results
+ *   "head_fuse_dbg"     integer, default 0: phase-kill timing variant of the fused head layer, WRONG results */
 int ach_set_option(ach_handle* h, const char* key, int32_t value);
+int ach_get_option(const ach_handle* h, const char* key, int32_t* value);
+const char* ach_option_key(int32_t index);
 
 /* Builds the launch plan and the activation arena for batch size B (re-plan to change B). */
 int ach_plan(ach_handle* h, int32_t batch);

@@ -907,3 +907,144 @@ def test_emulated_sparse_pool_stores_leave_the_same_map(sdt):
         for a_list, b_list in zip(res[other], res[0]):
             for a, b in zip(a_list, b_list):
                 assert torch.equal(a, b), other
+
+
+# ---- the option table (achelous_amd/csrc/engine_options.h) and plan invalidation, through the C ABI
+# every option's default, read off the members' initialisers in engine.h before the options became one table: the record that no default moved
+OPTION_DEFAULTS = {
+    'full_taps': 0, 'streams': 1, 'graph': 0, 'fused_mlp': 1, 'mlp_split': -1, 'row_conv': 1, 'fused_rc': 1, 'dw_tile': 1, 'stem_mfma': 1, 'point_stream2': -1,
+    'head_batch': 1, 'head_fuse': 1, 'head_fuse_dbg': 0, 'side_priority': 3, 'head_lds_pad': 0, 'head_stream': 0, 'split_decoders': 0, 'group_wpc': 4096,
+    'group_max': 1024, 'dec_fork': 1, 'radar_start': -2, 'pipeline': 0, 'pool_strip': 2, 'fused_mv2': 1, 'dw_even': 1, 'xca_mfma': 1, 'xca_frame': 0,
+    'xca_fold_mfma': 1, 'xca_slice': 0, 'xca_front_waves': 0, 'xca_back_waves': 0, 'gemm_rows': 1, 'radar_rows4': 2, 'radar_skip': 1, 'radar_bg': 1,
+    'radar_pool_sparse': 1, 'radar_compact': 1, 'head_mfma': 0, 'head_rows': 2, 'xwait2_op': -1, 'gemm_blocks': 0, 'sdta_fuse': 1, 'level_chain': 1,
+    'level_rows': 0, 'mlp_band': 1, 'mlp_band_run': 0, 'mlp_band_dbg': 0, 'mlp_band_lean': 0, 'head_band': 40, 'head_grid': 0, 'head_debug': 0, 'attn_mfma': 1,
+    'ds_fuse': 1, 'sa_fuse': 0, 'pn2_fps_all': 1, 'ghost_rb': 5, 'pc_chain': 1, 'mlp_split_hw': 1024, 'radar_direct': 1, 'mv_stem': 1, 'csp_fuse': 2,
+    'band_rows_s3': 0, 'spp_split': 0, 'ffn_rows2': 1, 'csp_band': 40, 'ghost_fuse': 1, 'io_bf16': 0}
+
+
+def _bare_engine(kw, dtype=DTYPE_F32):
+    from achelous_amd.engine import NativeEngine
+    return NativeEngine(emu_library(), num_det=kw['num_det'], num_seg=kw['num_seg'], phi=kw['phi'], backbone=kw['backbone'], resolution=kw['resolution'],
+                        pc_channels=kw['pc_channels'], pc_classes=kw['pc_classes'], num_points=16, nano_head=kw['nano_head'], spp=kw['spp'], dtype=dtype)
+
+
+def _option_keys():
+    L, keys = emu_library().lib, []
+    while L.ach_option_key(len(keys)) is not None:
+        keys.append(L.ach_option_key(len(keys)).decode())
+    return keys
+
+
+def test_option_table_and_header_agree():
+    """ach_option_key enumerates the table: 67 distinct keys, each documented (in double quotes) in the ach_set_option comment of include/achelous.h; a key
+    outside the table is refused by name."""
+    keys = _option_keys()
+    assert len(keys) == 67 and len(set(keys)) == 67, keys
+    header = open(os.path.join(os.path.dirname(GOLDEN_DIR), '..', 'include', 'achelous.h')).read()
+    comment = header[header.index('/* Options, set before ach_plan'):header.index('int ach_set_option(')]
+    assert [k for k in keys if f'"{k}"' not in comment] == []
+    kw, _, _ = _setup('en_s0', 64, 1, 16)
+    eng = _bare_engine(kw)
+    assert eng.L.ach_set_option(eng.h, b'no_such_option', 1) == -1                # ACH_ERR_INVALID
+    assert b'no_such_option' in eng.L.ach_last_error(eng.h)
+    assert eng.L.ach_set_option(eng.h, None, 1) == -1 and eng.L.ach_last_error(eng.h) == b'null option'
+    with pytest.raises(ValueError, match='unknown option: no_such_option'):
+        eng.get_option('no_such_option')
+
+
+def test_option_defaults_are_unchanged():
+    """An untouched handle reads every option at the default its member had before the table (OPTION_DEFAULTS), and a handle on which every key was SET to that
+    value builds the same plan."""
+    kw, sd, _ = _setup('en_s0', 64, 1, 16)
+    assert sorted(_option_keys()) == sorted(OPTION_DEFAULTS)
+    a, b = _bare_engine(kw), _bare_engine(kw)
+    assert {k: a.get_option(k) for k in OPTION_DEFAULTS} == OPTION_DEFAULTS
+    for k, v in OPTION_DEFAULTS.items():
+        b.set_option(k, v)
+    assert {k: b.get_option(k) for k in OPTION_DEFAULTS} == OPTION_DEFAULTS
+    for e in (a, b):
+        e.load_state_dict(sd)
+        e.plan(1)
+    assert a.launches() > 0 and a.op_table_full() == b.op_table_full()
+
+
+def test_option_rules_are_unchanged():
+    """set, then get: the normalisation of each kind of option (engine_options.h) is what ach_set_option's chain of comparisons applied."""
+    kw, _, _ = _setup('en_s0', 64, 1, 16)
+    eng = _bare_engine(kw)
+
+    def stored(key, value):
+        eng.set_option(key, value)
+        return eng.get_option(key)
+    for key, value, want in (('head_lds_pad', -5, 0), ('head_lds_pad', 70000, 65536), ('head_lds_pad', 4096, 4096), ('group_wpc', -1, 0), ('group_max', -1, 0),
+                             ('group_max', 256, 256), ('dec_fork', -1, 0), ('dec_fork', 9, 3), ('dec_fork', 2, 2), ('csp_fuse', -1, 0), ('csp_fuse', 5, 2),
+                             ('gemm_rows', 3, 1), ('gemm_rows', 2, 2), ('gemm_rows', 4, 4), ('gemm_rows', 0, 1), ('head_band', 0, 40), ('head_band', -3, 40),
+                             ('head_band', 16, 16), ('csp_band', 0, 40), ('csp_band', 8, 8), ('ghost_rb', 0, 5), ('ghost_rb', 3, 3), ('radar_skip', 7, 1),
+                             ('radar_skip', 0, 0), ('pipeline', -2, 1), ('radar_start', -2, -2), ('radar_start', 3, 3), ('mlp_split', -1, -1),
+                             ('xwait2_op', -1, -1), ('xwait2_op', 12, 12), ('split_decoders', 5, 5), ('side_priority', 2, 2)):
+        assert stored(key, value) == want, (key, value)
+    for dtype, ok in ((DTYPE_F32, False), (DTYPE_BF16, False), (DTYPE_F16, True)):
+        e = _bare_engine(kw, dtype)
+        if ok:
+            e.set_option('io_bf16', 1)
+        else:
+            with pytest.raises(ValueError, match='io_bf16'):
+                e.set_option('io_bf16', 1)
+        assert e.get_option('io_bf16') == (1 if ok else 0)
+        e.set_option('io_bf16', 0)
+        assert e.get_option('io_bf16') == 0
+
+
+def test_stale_plans_are_refused():
+    """Whatever a plan was built from invalidates it (include/achelous.h): after ach_load_weights or ach_set_option on a planned handle, ach_forward is
+    ACH_ERR_INVALID until ach_plan, and then equals a fresh engine's, bit for bit.  Forwards in flight on a pipelined handle can still be joined."""
+    kw, sd_a, (x, xr, xp) = _setup('en_s0', 64, 1, 16)
+    sd_b = condition_state_dict({k: torch.zeros_like(v) for k, v in sd_a.items()}, seed=1)
+    assert any(not torch.equal(sd_a[k], sd_b[k]) for k in sd_a)
+
+    def run(e):
+        o = alloc_outputs(kw, 1, 16, torch.float32, 'cpu')
+        e.forward(x, xr, xp, o)
+        return o
+    want_b = run(make_engine(emu_library(), kw, 1, sd_b, 16, DTYPE_F32, full_taps=False))
+    eng = make_engine(emu_library(), kw, 1, sd_a, 16, DTYPE_F32, full_taps=False)
+    got_a = run(eng)
+    assert not all(torch.equal(u, v) for u, v in zip(got_a, want_b))
+    eng.load_state_dict(sd_b)
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        run(eng)
+    assert eng.launches() == 0 and eng.tap_names() == []
+    eng.plan(1)
+    for u, v in zip(run(eng), want_b):
+        assert torch.equal(u, v)
+    # the same through an option: the raw ABI call, which (unlike NativeEngine.set_option) leaves the binding's own batch bookkeeping alone
+    assert eng.L.ach_set_option(eng.h, b'streams', 0) == 0
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        run(eng)
+    o = alloc_outputs(kw, 1, 16, torch.float32, 'cpu')
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        eng.forward_detect(x, xr, xp, o, torch.zeros(1, 84, 12), 0.3, 0.5, 4, torch.zeros(1, 4, 7), torch.zeros(1, 4, dtype=torch.int32),
+                           torch.zeros(1, dtype=torch.int32), torch.zeros(eng.nms_workspace_bytes(1), dtype=torch.uint8))
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        eng.forward_profiled(x, xr, xp, o)
+    eng.plan(1)
+    fresh = _bare_engine(kw)
+    fresh.set_option('streams', 0)
+    fresh.load_state_dict(sd_b)
+    fresh.plan(1)
+    assert eng.op_table_full() == fresh.op_table_full()
+    for u, v in zip(run(eng), run(fresh)):
+        assert torch.equal(u, v)
+    # a pipelined handle with one forward un-joined: an option drops the plan, not the forward
+    piped = _bare_engine(kw)
+    piped.set_option('pipeline', 1)
+    piped.load_state_dict(sd_b)
+    piped.plan(1)
+    o = run(piped)
+    assert piped.forwards_in_flight() == 1
+    piped.set_option('dec_fork', 2)
+    assert piped.forwards_in_flight() == 1
+    piped.join()
+    assert piped.forwards_in_flight() == 0
+    for u, v in zip(o, want_b):
+        assert torch.equal(u, v)

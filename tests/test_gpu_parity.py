@@ -719,8 +719,8 @@ def test_fused_kernels_agree_with_the_layerwise_path(option):
         with torch.no_grad():
             ref = m(xs, rs, ps)
             e = _engine_of(m, dt)
-            default = 0 if option in ('split_decoders', 'head_mfma', 'head_stream') else 1
-            e.set_option(option, 1 - default)
+            default = e.get_option(option)
+            e.set_option(option, 0 if default else 1)
             e.plan(2)
             alt = m(xs, rs, ps)
             torch.cuda.synchronize()
@@ -1251,3 +1251,59 @@ def test_packed_fp16_deformable_blend_stays_within_a_few_fp16_ulps_of_the_fp32_b
     ratios = {k: _rel(a.float(), b.float()) / H16_TOL[k] for k, (a, b) in zip(('det0', 'det1', 'det2', 'se_seg', 'lane_seg', 'pc_seg'), zip(res['pk16'][1], res['blend32'][1]))}
     print('packed fp16 blend vs fp32 blend, outputs as fractions of the 16-bit bounds:', {k: round(v, 3) for k, v in ratios.items()})
     assert all(v < 0.75 for v in ratios.values()), ratios
+
+
+@pytest.mark.parametrize('dtype', ['f32', 'f16'])
+def test_stale_plans_are_refused(dtype):
+    """Through the C ABI of the HIP library (include/achelous.h): ach_load_weights or ach_set_option on a planned handle drops the plan — ach_forward is
+    ACH_ERR_INVALID until ach_plan, and then equals, bit for bit, a fresh engine built from the new weights / option.  A forward in flight on a pipelined
+    handle can still be joined after an option was set."""
+    from emu_util import alloc_outputs
+    g = Golden('en_s0')
+    kw = ctor_kwargs(g.meta)
+    blank = Achelous(**kw).state_dict()
+    sd_a = g.calibrate(condition_state_dict(blank, seed=g.meta['weight_seed']))
+    sd_b = g.calibrate(condition_state_dict(blank, seed=g.meta['weight_seed'] + 1))
+    code, td = {'f32': (eng_mod.DTYPE_F32, torch.float32), 'f16': (eng_mod.DTYPE_F16, torch.float16)}[dtype]
+    x, xr, xp = (t.cuda().to(td) for t in make_inputs(1, 41, resolution=kw['resolution'], pc_channels=kw['pc_channels']))
+
+    def engine(sd, **options):
+        e = eng_mod.NativeEngine(eng_mod.hip_library(), num_det=kw['num_det'], num_seg=kw['num_seg'], phi=kw['phi'], backbone=kw['backbone'],
+                                 resolution=kw['resolution'], pc_channels=kw['pc_channels'], pc_classes=kw['pc_classes'], num_points=xp.shape[2],
+                                 nano_head=kw['nano_head'], spp=kw['spp'], dtype=code, neck=kw['neck'], pc_seg=kw['pc_seg'])
+        for k, v in options.items():
+            e.set_option(k, v)
+        e.load_state_dict(sd)
+        e.plan(1)
+        return e
+
+    def run(e):
+        o = alloc_outputs(kw, 1, xp.shape[2], td, 'cuda')
+        e.forward(x, xr, xp, o, torch.cuda.current_stream().cuda_stream)
+        return o
+
+    def same(a, b):
+        torch.cuda.synchronize()
+        return all(torch.equal(u, v) for u, v in zip(a, b))
+    want_b = run(engine(sd_b))
+    eng = engine(sd_a)
+    assert not same(run(eng), want_b)
+    eng.load_state_dict(sd_b)
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        run(eng)
+    eng.plan(1)
+    assert same(run(eng), want_b)
+    torch.cuda.synchronize()
+    assert eng.L.ach_set_option(eng.h, b'streams', 0) == 0           # the raw call: NativeEngine.set_option keeps bookkeeping of its own
+    with pytest.raises(ValueError, match='ach_plan must precede'):
+        run(eng)
+    eng.plan(1)
+    fresh = engine(sd_b, streams=0)
+    assert eng.op_table_full() == fresh.op_table_full()
+    assert same(run(eng), run(fresh)) and same(run(eng), want_b)
+    piped = engine(sd_b, pipeline=1)
+    o = run(piped)
+    assert piped.forwards_in_flight() == 1
+    piped.set_option('dec_fork', 2)
+    piped.join(torch.cuda.current_stream().cuda_stream)
+    assert piped.forwards_in_flight() == 0 and same(o, want_b)
