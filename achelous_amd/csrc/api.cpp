@@ -19,6 +19,7 @@
 #include "k_data.h"
 #include "k_radarmap.h"
 #include "k_serve.h"
+#include "k_draw.h"
 
 struct ach_handle {
     ach::EngineBase* eng = nullptr;
@@ -1010,6 +1011,44 @@ int ach_correct_boxes_frames(ach_handle* h, int32_t batch, int32_t max_det, cons
         train_need(batch > 0 && max_det > 0 && rows && count && shapes_host && shapes_dev && out_rows, "ach_correct_boxes_frames");
         for (int b = 0; b < batch; ++b) train_need(shapes_host[2 * b] >= 1 && shapes_host[2 * b + 1] >= 1, "ach_correct_boxes_frames: a frame's H and W are at least 1");
         h->eng->correct_boxes_frames(batch, max_det, rows, count, shapes_dev, letterbox, out_rows, static_cast<hipStream_t>(stream));
+    });
+}
+
+// ---- drawing the kept detections on served frames (k_draw.h): box rings, label plates and label text of a ragged batch in two launches, in place.  Stateless.
+// Every host table is checked before anything is launched; what comes from DEVICE data (count, class id, score, coordinates) is bounded by the kernels themselves.
+int ach_draw_detections_frames(uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, int32_t batch, const float* boxes,
+                               const int32_t* count, int32_t max_det, int32_t num_classes, const int32_t* labels_host, const int32_t* labels_dev, int64_t num_labels,
+                               const uint8_t* blob_dev, int64_t blob_bytes, const uint8_t* style_dev, int32_t* records, int32_t* class_counts, void* stream) {
+    return train_guard([&] {
+        train_need(arena && table_host && table_dev && boxes && count && labels_host && labels_dev && blob_dev && style_dev && records && batch > 0 && batch <= 65535 &&
+                   arena_bytes > 0 && num_labels > 0 && num_labels < (1L << 24) && blob_bytes >= 0, "ach_draw_detections_frames");
+        train_need(max_det >= 1 && max_det <= ach::DRAW_MAX_DET, "ach_draw_detections_frames: max_det is 1..1024");
+        train_need(num_classes >= 1 && num_classes <= ach::DRAW_MAX_CLASSES, "ach_draw_detections_frames: num_classes is 1..256");
+        train_need((reinterpret_cast<uintptr_t>(arena) & 3u) == 0 && (reinterpret_cast<uintptr_t>(records) & 15u) == 0,
+                   "ach_draw_detections_frames: the arena is 4-byte aligned and the record workspace 16-byte aligned");
+        for (int64_t l = 0; l < num_labels; ++l) {
+            const int32_t* L = labels_host + l * ach::DRAW_LABEL_COLS;
+            train_need(L[0] >= 0 && L[1] >= 0 && L[2] >= 0 && L[1] <= 4096 && L[2] <= 4096 && int64_t(L[1]) * L[2] <= blob_bytes - L[0],
+                       "ach_draw_detections_frames: a label's mask passes the atlas blob");
+            train_need(L[3] >= -65536 && L[3] <= 65536 && L[4] >= -65536 && L[4] <= 65536 && L[5] >= 0 && L[5] <= 65536 && L[6] >= 0 && L[6] <= 65536,
+                       "ach_draw_detections_frames: a label's offsets and size are out of range");
+        }
+        long blocks = 0;
+        for (int b = 0; b < batch; ++b) {
+            const int64_t* f = table_host + long(b) * ach::DRAW_TABLE_COLS;
+            const int64_t off = f[0], H = f[1], W = f[2], pitch = f[3];
+            train_need(H >= 1 && W >= 1 && H <= (1L << 20) && W <= (1L << 20), "ach_draw_detections_frames: a frame's H and W are 1..2^20");
+            train_need(pitch >= 3 * W && pitch % 4 == 0 && pitch < (1L << 32) && off >= 0 && off % 4 == 0 && off <= arena_bytes && H * pitch <= arena_bytes - off,
+                       "ach_draw_detections_frames: a frame's extent passes the arena (offset and pitch are multiples of 4, pitch >= 3 W)");
+            train_need(f[4] >= 1 && f[4] <= ach::DRAW_MAX_THICKNESS, "ach_draw_detections_frames: thickness is 1..64");
+            train_need(f[5] >= 0 && f[5] <= num_labels - int64_t(num_classes) * ach::DRAW_SCORES, "ach_draw_detections_frames: a frame's atlas base passes the label table");
+            blocks = std::max(blocks, ach::cdivl(W, ach::DRAW_TW) * ach::cdivl(H, ach::DRAW_TH));
+        }
+        train_need(blocks < (1L << 31), "ach_draw_detections_frames: a frame is too large");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        ach::DrawParams p{boxes, count, records, arena, reinterpret_cast<const long long*>(table_dev), labels_dev, blob_dev, style_dev, class_counts, max_det, num_classes};
+        ACH_LAUNCH(ach::draw_prepare_kernel, dim3(unsigned(batch)), dim3(256), s, p);
+        ACH_LAUNCH(ach::draw_tiles_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
     });
 }
 

@@ -41,7 +41,7 @@ class NativeLibrary:
                'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
                'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
                'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss',
-               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch', 'ach_data_radar_maps', 'ach_data_radar_points', 'ach_seg_overlay_frames', 'ach_correct_boxes_frames')
+               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch', 'ach_data_radar_maps', 'ach_data_radar_points', 'ach_seg_overlay_frames', 'ach_correct_boxes_frames', 'ach_draw_detections_frames')
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -159,7 +159,8 @@ class NativeLibrary:
                            ('ach_data_radar_maps', [vp, i64, i32, vp, vp, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp, i64, vp, i32, vp]),
                            ('ach_data_radar_points', [vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
                            ('ach_seg_overlay_frames', [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, i64, vp, i64, vp, i64, vp]),
-                           ('ach_correct_boxes_frames', [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp])):
+                           ('ach_correct_boxes_frames', [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]),
+                           ('ach_draw_detections_frames', [vp, i64, vp, vp, i32, vp, vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp])):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = ctypes.c_int
         L.ach_record_words.argtypes = [i32, i32]

@@ -9,6 +9,7 @@
     correct_boxes_frames(rows, cnt, (R, R), shapes)  utils_bbox.py:5-30     -> [B,max_det,7]     every frame's own (H, W)
     detect_frames(net, frames, radar, points)        achelous.py:190-345    camera bytes of B frames of different sizes -> boxes, class maps, overlays
     detect_frames_from_clouds(net, frames, clouds)   + radar_feature_map_generate.ipynb   the same from raw radar point clouds (data.radar_maps_batch / radar_points_batch)
+    draw_detections_frames(arena, layout, boxes, ..) achelous.py:363-433    box rings, label plates and label text drawn in place on every frame, PIL's bytes (csrc/k_draw.h)
 HIP kernels through the C ABI; no CPU fallback.
 """
 import contextlib
@@ -17,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from ._native import lib as _pass_lib, check as _check, stream as _stream, stateless_handle
+from ._native import lib as _pass_lib, check as _check, ptr as _ptr, stream as _stream, stateless_handle
 from .postprocess import _handle
 
 # `_pass_lib(t)` is `_native.lib` (tests set `_pass_lib.test_library`): it raises RuntimeError for a CPU tensor.  The single-shape entries below always run on the
@@ -359,9 +360,181 @@ def correct_boxes_frames(rows, cnt, input_shape, shapes, letterbox_image):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- boxes, plates and labels on the frames (csrc/k_draw.h)
+DRAW_TABLE_COLS, DRAW_LABEL_COLS, DRAW_REC, DRAW_SCORES = 8, 7, 16, 101        # k_draw.h
+DRAW_STYLE_BYTES, DRAW_STYLE_SKIP, DRAW_STYLE_INK = 1028, 768, 1024
+_DRAW_ERRORS = {-1: ValueError, -2: NotImplementedError}
+
+
+def class_colors(n):
+    """the reference's box colours (achelous.py:130-132): the HSV wheel in n steps, truncated to bytes; uint8 [n, 3]"""
+    import colorsys
+    return np.array([[int(v * 255) for v in colorsys.hsv_to_rgb(x / n, 1., 1.)] for x in range(n)], dtype=np.uint8).reshape(n, 3)
+
+
+def _core_bytes(core):
+    """the rows of an 'L' ImagingCore (what font.getmask2 returns) as uint8 [h, w]"""
+    w, h = core.size
+    return np.frombuffer(bytes(core), dtype=np.uint8).reshape(h, w) if w and h else np.zeros((h, w), np.uint8)
+
+
+class LabelAtlas:
+    """Every label the drawing can need at ONE font size, rendered once on the host with PIL: for class c and hundredths k the text '{name} {k / 100:.2f}' as the
+    8-bit coverage mask `font.getmask2(label, 'L', anchor='la')` returns, packed into one uint8 `blob`, and `table` int32 [num_classes * 101, 7] = (byte offset, mask w,
+    mask h, ox, oy, label_w, label_h): (ox, oy) is where ImageDraw.text puts the mask relative to the text origin, (label_w, label_h) = textbbox((0, 0), label, font)[2:4]
+    (what the removed `textsize` returned).  `font`: None = ImageFont.load_default(size), a path for ImageFont.truetype, or a callable size -> ImageFont.
+    `LabelAtlas.get` caches per (names, font, size); `from_arrays` builds one from stored arrays without PIL and puts it in that cache."""
+    _cache = {}
+
+    def __init__(self, class_names, font_size, font=None, _arrays=None):
+        self.class_names, self.font_size, self.font = tuple(str(n) for n in class_names), int(font_size), font
+        if _arrays is None:
+            from PIL import Image, ImageDraw, ImageFont
+            fnt = font(self.font_size) if callable(font) else ImageFont.load_default(self.font_size) if font is None else ImageFont.truetype(font, self.font_size)
+            draw = ImageDraw.Draw(Image.new('RGB', (1, 1)))
+            table, masks, off = np.zeros((len(self.class_names) * DRAW_SCORES, DRAW_LABEL_COLS), np.int32), [], 0
+            for c, name in enumerate(self.class_names):
+                for k in range(DRAW_SCORES):
+                    label = '{} {:.2f}'.format(name, k / 100)
+                    core, (ox, oy) = fnt.getmask2(label, 'L', anchor='la')
+                    m = _core_bytes(core)
+                    lw, lh = draw.textbbox((0, 0), label, font=fnt)[2:4]
+                    table[c * DRAW_SCORES + k] = (off, m.shape[1], m.shape[0], ox, oy, lw, lh)
+                    masks.append(m.reshape(-1))
+                    off += m.size
+            _arrays = (table, np.concatenate(masks) if off else np.zeros(0, np.uint8))
+        self.table = np.ascontiguousarray(_arrays[0], dtype=np.int32).reshape(-1, DRAW_LABEL_COLS)
+        self.blob = np.ascontiguousarray(_arrays[1], dtype=np.uint8).reshape(-1)
+        if len(self.table) != len(self.class_names) * DRAW_SCORES:
+            raise ValueError("LabelAtlas: the table holds 101 labels per class, 7 numbers each")
+
+    @classmethod
+    def from_arrays(cls, class_names, font_size, table, blob, font=None):
+        a = cls(class_names, font_size, font, _arrays=(table, blob))
+        cls._cache[(a.class_names, font, a.font_size)] = a
+        for key in [k for k in _DRAW_ATLASES if k[:2] == (a.class_names, font) and a.font_size in k[2]]:
+            del _DRAW_ATLASES[key]                           # device copies that hold the arrays this call replaces
+        return a
+
+    @classmethod
+    def get(cls, class_names, font_size, font=None):
+        key = (tuple(str(n) for n in class_names), font, int(font_size))
+        if key not in cls._cache:
+            cls._cache[key] = cls(class_names, font_size, font)
+        return cls._cache[key]
+
+
+class DrawStyle:
+    """How `draw_detections_frames` draws: `class_names` (the label texts; their number is num_classes, at most 256), `colors` uint8 [num_classes, 3] (None: the
+    reference's `class_colors`), `skip`: class names or ids that are not drawn (the reference skips 'sailor'), `font` as `LabelAtlas` takes it, `ink` the text colour.
+    `font_size` / `thickness`: None = the reference's rules per frame, floor(0.03 H + 0.5) and max((W + H) // mean(input_shape), 1); a number fixes it for every frame (`thickness` may also be one number per frame)."""
+
+    def __init__(self, class_names, colors=None, skip=(), font=None, ink=(0, 0, 0), font_size=None, thickness=None):
+        self.class_names = tuple(str(n) for n in class_names)
+        n = len(self.class_names)
+        if not 1 <= n <= 256:
+            raise ValueError("DrawStyle: 1..256 class names")
+        self.colors = class_colors(n) if colors is None else np.asarray(colors, dtype=np.uint8).reshape(n, 3)
+        self.skip = tuple(sorted(self.class_names.index(k) if isinstance(k, str) else int(k) for k in skip))
+        if any(k < 0 or k >= n for k in self.skip):
+            raise ValueError("DrawStyle: `skip` names classes of `class_names`")
+        self.font, self.ink, self.font_size, self.thickness = font, tuple(int(v) for v in ink), font_size, thickness
+        b = np.zeros(DRAW_STYLE_BYTES, np.uint8)
+        b[:3 * n] = self.colors.reshape(-1)
+        b[[DRAW_STYLE_SKIP + k for k in self.skip]] = 1
+        b[DRAW_STYLE_INK:DRAW_STYLE_INK + 3] = self.ink
+        self.bytes = b
+
+    def font_size_for(self, h):
+        return int(np.floor(3e-2 * h + 0.5)) if self.font_size is None else int(self.font_size)
+
+    def thickness_for(self, b, h, w, input_shape):
+        if self.thickness is None:
+            return int(max((w + h) // np.mean(input_shape), 1))
+        if not hasattr(self.thickness, '__len__'):
+            return int(self.thickness)
+        if b >= len(self.thickness):
+            raise ValueError(f"DrawStyle: `thickness` holds {len(self.thickness)} values for a batch with a frame {b}")
+        return int(self.thickness[b])
+
+
+_DRAW_ATLASES = {}                 # insertion-ordered; at most _DRAW_ATLASES_MAX entries, the oldest dropped first
+_DRAW_ATLASES_MAX = 16
+
+
+def _device_atlases(style, sizes, device):
+    """the atlases of the font sizes one call needs, concatenated: (host label table, its device copy, device blob, {size: first entry}); cached per (names, font, sizes,
+    device), so only the first call with a new set of sizes renders and uploads anything.  The cache is bounded: a stream of ever new sets of frame heights keeps the 16
+    newest sets and uploads again for an older one; `LabelAtlas.from_arrays` drops the entries that hold the arrays it replaces."""
+    key = (style.class_names, style.font, sizes, str(device))
+    if key not in _DRAW_ATLASES:
+        while len(_DRAW_ATLASES) >= _DRAW_ATLASES_MAX:
+            del _DRAW_ATLASES[next(iter(_DRAW_ATLASES))]
+        tables, blobs, base, off = [], [], {}, 0
+        for size in sizes:
+            a = LabelAtlas.get(style.class_names, size, style.font)
+            t = a.table.copy()
+            t[:, 0] += off
+            base[size] = sum(len(x) for x in tables)
+            tables.append(t)
+            blobs.append(a.blob)
+            off += a.blob.size
+        host = np.ascontiguousarray(np.concatenate(tables))
+        blob = np.concatenate(blobs + [np.zeros(16, np.uint8)])
+        _DRAW_ATLASES[key] = (host, torch.from_numpy(host).to(device), torch.from_numpy(blob).to(device), base, off)
+    return _DRAW_ATLASES[key]
+
+
+def draw_detections_frames(arena, layout, boxes, count, shapes, style, input_shape, class_counts=None):
+    """The drawing the reference's detect_image ends with (achelous.py:400-433), for B frames of different sizes, IN PLACE and byte for byte PIL's: per kept detection
+    `boxes[b, j]`, j < count[b], in that order — later drawing overwrites earlier — `thickness` one-pixel rings of the box in the class colour, the filled label plate
+    above the box (inside it when there is no room) and the label '{name} {obj * cls:.2f}' in `style.ink`.  Rows whose class is in `style.skip`, whose id is outside
+    [0, num_classes) or that hold a non-finite number are not drawn.
+
+    arena: 1-D uint8 tensor of packed HWC frames; layout: (byte offsets, pitches) per frame, or what `frames_layout(shapes)` returns (its overlay part is used) — offsets
+    and pitches are multiples of 4, as `seg_maps_frames` lays its overlay arena out.  boxes [B, max_det, 7] fp32 and count [B] int32 as `correct_boxes_frames` returns
+    them, `shapes` one (H, W) per frame, `style` a `DrawStyle`, `input_shape` the network's (R, R).  class_counts: optional int32 [B, num_classes] tensor that receives
+    the number of kept rows per class id (the reference's count=True tally; skipped classes count, rows past count[b] do not).
+    Two launches whatever B is; the per-frame table travels in one non-blocking copy; no host read, no synchronisation.  Returns the per-frame [H, W, 3] views.
+    Not covered: crop=True (data-dependent output sizes), the matplotlib scatter of the point classes, the heat-map mode, file output."""
+    from . import data as _data
+    lib = _pass_lib(arena)
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError("draw_detections_frames: `arena` is a contiguous 1-D uint8 tensor")
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[2] != 7 or count.dtype != torch.int32 or count.numel() != boxes.shape[0]:
+        raise ValueError("draw_detections_frames: boxes [B, max_det, 7] float32 and count [B] int32 expected")
+    if boxes.device != arena.device or count.device != arena.device:
+        raise ValueError("draw_detections_frames: boxes, count and the arena live on one device")
+    boxes, count = boxes.contiguous(), count.contiguous()
+    B, max_det, _ = boxes.shape
+    shapes = _frame_shapes(shapes, B)
+    offs, pitches = (layout[3], layout[4]) if len(layout) == 6 else layout
+    if len(offs) != B or len(pitches) != B:
+        raise ValueError("draw_detections_frames: one offset and one pitch per frame")
+    nc = len(style.class_names)
+    if class_counts is not None and (class_counts.dtype != torch.int32 or tuple(class_counts.shape) != (B, nc) or not class_counts.is_contiguous() or class_counts.device != arena.device):
+        raise ValueError("draw_detections_frames: class_counts is a contiguous int32 [B, num_classes] tensor on the arena's device")
+    sizes = [style.font_size_for(h) for h, w in shapes]
+    labels_host, labels_dev, blob_dev, base, blob_bytes = _device_atlases(style, tuple(sorted(set(sizes))), arena.device)
+    table = np.zeros((B, DRAW_TABLE_COLS), np.int64)
+    for b, (h, w) in enumerate(shapes):
+        table[b, :6] = (int(offs[b]), h, w, int(pitches[b]), style.thickness_for(b, h, w, input_shape), base[sizes[b]])
+    meta = _data._Meta(arena.device, 'serve_draw')
+    tref, sref = meta.add(table), meta.add(style.bytes)
+    meta.commit()
+    recs = torch.empty(B * max_det * DRAW_REC, dtype=torch.int32, device=arena.device)
+    ctx = torch.cuda.device(arena.device) if arena.is_cuda else contextlib.nullcontext()
+    with ctx:
+        _check(lib, lib.lib.ach_draw_detections_frames(_ptr(arena), arena.numel(), meta.host_ptr(tref), meta.dev_ptr(tref), B, _ptr(boxes), _ptr(count), max_det, nc,
+                                                       labels_host.ctypes.data, _ptr(labels_dev), len(labels_host), _ptr(blob_dev), blob_bytes, meta.dev_ptr(sref),
+                                                       _ptr(recs), _ptr(class_counts), _stream(arena)), _DRAW_ERRORS, 'draw kernels')
+    return [torch.as_strided(arena, (h, w, 3), (int(pitches[b]), 3, 1), int(offs[b])) for b, (h, w) in enumerate(shapes)]
+
+
 def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4, letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True,
-                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3):
-    """`detect_frame` for B frames of DIFFERENT sizes: the arithmetic of the reference's detect_image (achelous.py:190-345) without its file I/O and box drawing.
+                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3, draw=None):
+    """`detect_frame` for B frames of DIFFERENT sizes: the arithmetic of the reference's detect_image (achelous.py:190-433) without its file I/O; the box drawing
+    (achelous.py:363-433) is on with `draw`.
 
     frames: a list of CPU uint8 [H_i, W_i, 3] arrays / tensors, or a `data.Arena` already on the device; radar_maps [B, 3, R, R] float and points
     [B, N, pc_channels] float on the GPU.  One upload (`data.pack_arena`), the letterbox of all frames in two launches (`data.letterbox_batch`; with
@@ -370,18 +543,26 @@ def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4
     boxes are NOT cut to their count here: the caller slices `boxes[b, :count[b]]` when it reads `count`.
 
     Returns dict(boxes [B, max_det, 7] = (y1, x1, y2, x2 in the frame's own pixels, obj, class conf, class id), rows past count[b] zero; count [B] int32;
-    semantic, waterline: lists of [H_i, W_i] uint8 views; overlay: list of [H_i, W_i, 3] uint8 views (overlay=True; `seg_maps_frames`); point_class [B, N] int64)."""
+    semantic, waterline: lists of [H_i, W_i] uint8 views; overlay: list of [H_i, W_i, 3] uint8 views (overlay=True; `seg_maps_frames`); point_class [B, N] int64).
+    draw: None, or a `DrawStyle` — two more launches (`draw_detections_frames`) then draw every kept detection's box, plate and label on the overlay (overlay=True
+    is required), and the result gains class_counts [B, num_classes] int32, the kept rows per class id.  With draw=None nothing changes."""
     from . import data as _data
+    _need_overlay(draw, overlay)
     R = net.resolution
     arena = _data._as_arena(frames, 3, radar_maps.device, 'images')
     B = len(arena.frames)
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = preprocess_input_radar(radar_maps, dtype)
     xp = normalize_points(points, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw)
 
 
-def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness):
+def _need_overlay(draw, overlay):
+    if draw is not None and not overlay:
+        raise ValueError("detect_frames: `draw` draws on the overlay, so it needs overlay=True")
+
+
+def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw=None):
     """`detect_frames` from the three prepared network inputs on"""
     R, B = net.resolution, len(arena.frames)
     shapes = [(f[1], f[2]) for f in arena.frames]
@@ -392,18 +573,22 @@ def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_ima
     res = {'boxes': boxes, 'count': cnt, 'semantic': maps['semantic'], 'waterline': maps['waterline'], 'point_class': pc.float().argmax(-1)}
     if overlay:
         res['overlay'] = maps['overlay']
+    if draw is not None:
+        res['class_counts'] = torch.empty(B, len(draw.class_names), dtype=torch.int32, device=boxes.device)
+        draw_detections_frames(maps['arenas']['overlay'], frames_layout(shapes), boxes, cnt, shapes, draw, (R, R), res['class_counts'])
     return res
 
 
 def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_points=512, columns=None, point_columns=None, cell=None, conf_thres=0.5, nms_thres=0.4,
                               letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE,
-                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda'):
+                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda', draw=None):
     """`detect_frames` from raw radar point clouds instead of ready radar maps and sampled points: `clouds` is a list of CPU float32 / float64 arrays [n_i, F] (or
     `data.Clouds` already on the device), uploaded once.  The normalised radar map is `data.radar_maps_batch(..., normalize=True)` (the reference's offline
     rasterisation, then its min-max scaling: `columns` = the columns of range, doppler, rcs, u, v, default 0..4; `cell` default (6.0, 3.375)); the points are
     `data.radar_points_batch`: `num_points` rows per frame by `indices` [B, N] or drawn from `rng`, the columns `point_columns` (default: the first
     `net.pc_channels`), normalised.  Two launches for the map and one for the points whatever B is, nothing read back; everything else and the result as `detect_frames`."""
     from . import data as _data
+    _need_overlay(draw, overlay)
     R = net.resolution
     packed = _data._as_clouds(clouds, device)
     arena = _data._as_arena(frames, 3, packed.data.device, 'images')
@@ -413,4 +598,4 @@ def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_p
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = _data.radar_maps_batch(packed, R, _data.MAP_COLUMNS if columns is None else columns, _data.CELL if cell is None else cell, True, dtype)
     xp, _ = _data.radar_points_batch(packed, tuple(range(net.pc_channels)) if point_columns is None else point_columns, None, num_points, indices, rng, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw)

@@ -271,6 +271,25 @@ int ach_seg_overlay_frames(ach_handle* h, int32_t batch, int32_t channels, const
 int ach_correct_boxes_frames(ach_handle* h, int32_t batch, int32_t max_det, const float* rows, const int32_t* count, const int32_t* shapes_host,
                              const int32_t* shapes_dev, int32_t letterbox, float* out_rows, void* stream);
 
+/* The drawing detect_image ends with (achelous.py:363-433) for a ragged batch, IN PLACE, in two launches whatever the batch (achelous_amd/csrc/k_draw.h): per
+ * kept detection, in the order of boxes[b, :count[b]], `thickness` one-pixel rings of the box in the class colour, the filled label plate and the label text
+ * '{name} {obj * cls:.2f}' — byte for byte what PIL's ImageDraw.rectangle / ImageDraw.text leave.  Stateless (no handle).
+ *   arena        packed HWC uint8 frames (4-byte aligned), e.g. the overlay arena of ach_seg_overlay_frames.
+ *   frame table  int64 [batch][8], host copy and device copy: 0 byte offset of the frame (a multiple of 4), 1 H, 2 W, 3 pitch (>= 3 W, a multiple of 4),
+ *                4 ring thickness (1..64), 5 first entry of the frame's font size in the label table, 6-7 unused.
+ *   boxes, count device [batch, max_det, 7] = (y1, x1, y2, x2 in the frame's pixels, obj, class conf, class id) and int32 [batch], as ach_correct_boxes_frames
+ *                leaves them.  A row is skipped if its class is flagged in `style`, its id is outside [0, num_classes) or one of its six floats is not finite;
+ *                count is clamped to max_det (1..1024) and coordinates are clamped on the device.
+ *   label table  int32 [num_labels][7], host and device copy; entry base + class * 101 + hundredths: 0 byte offset of the glyph mask (8-bit coverage, w * h
+ *                bytes) in `blob_dev`, 1 mask w, 2 mask h, 3 ox, 4 oy (mask position relative to the text origin), 5 label w, 6 label h.
+ *   style_dev    uint8 [1028]: class colours [256][3], skip flag per class [256], ink [3], pad.
+ *   records      workspace, int32 [batch * max_det * 16], 16-byte aligned.  class_counts: optional int32 [batch, num_classes], the kept rows per class id.
+ * The host copies are checked before anything is launched: a frame past the arena, a bad pitch or alignment, thickness outside 1..64, num_classes outside
+ * 1..256, a label mask past the blob, an atlas base past the label table -> ACH_ERR_INVALID, no launch. */
+int ach_draw_detections_frames(uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, int32_t batch, const float* boxes,
+                               const int32_t* count, int32_t max_det, int32_t num_classes, const int32_t* labels_host, const int32_t* labels_dev, int64_t num_labels,
+                               const uint8_t* blob_dev, int64_t blob_bytes, const uint8_t* style_dev, int32_t* records, int32_t* class_counts, void* stream);
+
 /* Range guard of the fp16-storage engine (ACH_DTYPE_F16).  The reference runs fp32 or, under autocast, fp16 WITH torch's GradScaler / inf checks
  * (utils/utils_fit.py:120-166); bf16 callers (BASELINE configs[1]) are served by fp16 storage inside, which overflows at 65504 where bf16 does not.
  * Every kernel of that engine therefore runs with MODE.FP16_OVFL (overflowing conversions clamp to +-65504, never infinity), and this entry counts the
