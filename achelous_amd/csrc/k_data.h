@@ -9,7 +9,7 @@
 //   label table  int64 [B][16]: 0 nw, 1 nh, 2 dx, 3 dy, then per map (semantic at 4, water line at 10): byte offset (< 0: no such map -> zeros), H, W, pitch,
 //                column index table [nw], row index table [nh] (source index per resized sample, -1: none).
 // Bounds / coefficients are Pillow's precompute_coeffs + normalize_coeffs_8bpc over the whole axis (22-bit fixed point), as for resample_pass_kernel
-// (k_prepost.h); the index tables are Pillow's running double sum, which no closed form reproduces.  The C entries (api.cpp) check every extent
+// (k_prepost.h); the index tables are Pillow's running double sum, which no closed form reproduces.  The C entries (api_frames.cpp) check every extent
 // and every table entry on the host before anything is launched: the kernels themselves trust the tables.
 #pragma once
 #include "ach_platform.h"

@@ -10,7 +10,7 @@
 //                in its arena, 10 pitch of both maps, 11 byte offset of the overlay in its arena, 12 overlay pitch, 13-15 unused.
 //   constants   2304 bytes on the device: semantic palette [256][3], water-line palette [256][3], semantic remap [256], water-line remap [256], brightness
 //                table [256].  overlay = lut[blend(blend(image, pal_se[remap_se[class]], a1), pal_line[remap_line[line class]], a2)].
-// The C entry (api.cpp ach_seg_overlay_frames) checks every extent, pitch and alignment on the host before the launch: the kernel trusts the table.
+// The C entry (api_frames.cpp ach_seg_overlay_frames) checks every extent, pitch and alignment on the host before the launch: the kernel trusts the table.
 //
 // Arithmetic.  Class maps: coordinate float((double(d) + 0.5) * s - 0.5), the clamps, horizontal blend then vertical blend in fp32, first maximum — operation for
 // operation what seg_resize_argmax_kernel computes (serve_hblend / serve_vblend below say exactly what that is on the device).  That order rules out a vertical-first separable pass, but the HORIZONTAL blends are shared: at a

@@ -6,11 +6,13 @@ There is NO fallback: if the HIP library cannot be loaded, or a tensor is not on
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIBRARY = os.path.join(_HERE, 'libachelous_hip.so')
+HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'achelous.h')
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # include/achelous.h ACH_DTYPE_*: storage type of the activations (F16: inputs / outputs fp16, or bf16 with option io_bf16)
 BACKBONES = {'en': 0, 'mv': 1}
@@ -31,176 +33,57 @@ class AchTensorDesc(ctypes.Structure):
                 ('shape', ctypes.c_int64 * 4)]
 
 
+_SCALARS = {'void': None, 'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
+            'float': ctypes.c_float, 'double': ctypes.c_double}
+
+
+def _ctype(decl):
+    """the ctypes class of one C type as the header spells it: every pointer is c_void_p (byref(), ctypes arrays and pointer instances all pass as one),
+    `const char*` is c_char_p, a scalar is looked up by name; anything else raises"""
+    words = [w for w in decl.replace('*', ' ').split() if w != 'const']
+    if '*' in decl:
+        return ctypes.c_char_p if words == ['char'] and decl.count('*') == 1 else ctypes.c_void_p
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise ValueError(f'include/achelous.h: no ctypes class for the type {decl.strip()!r}')
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """{entry: (restype, [argtypes])} of every `RET ach_name(ARGS);` in the text of include/achelous.h, in the header's order"""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', '', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    protos = {}
+    for ret, name, args in re.findall(r'([\w\s*]+?)\b(ach_\w+)\s*\(([^()]*)\)\s*;', text):
+        argtypes = []
+        for arg in ([] if args.strip() == 'void' else args.split(',')):
+            m = re.fullmatch(r'\s*(.*?)\b\w+\s*(\[\d*\])?\s*', arg, flags=re.S)          # type, name, the array form `int64_t shape[4]`
+            if not m:
+                raise ValueError(f'include/achelous.h: {name}: cannot read the parameter {arg.strip()!r}')
+            argtypes.append(_ctype(m.group(1) + ('*' if m.group(2) else '')))
+        protos[name] = (_ctype(ret), argtypes)
+    return protos
+
+
+with open(HEADER) as _f:
+    PROTOTYPES = parse_header(_f.read())
+
+
 class NativeLibrary:
-    """dlopen + prototypes for every symbol declared in include/achelous.h."""
-    SYMBOLS = ('ach_create', 'ach_destroy', 'ach_last_error', 'ach_load_weights', 'ach_plan', 'ach_arena_bytes',
-               'ach_forward', 'ach_forward_detect', 'ach_join', 'ach_forwards_in_flight', 'ach_decode', 'ach_nms_workspace_bytes', 'ach_nms', 'ach_tap_count', 'ach_tap_name',
-               'ach_tap_shape', 'ach_read_tap', 'ach_plan_launches', 'ach_op_name', 'ach_op_bytes', 'ach_op_layout_bytes', 'ach_op_flops', 'ach_op_stream',
-               'ach_forward_profiled', 'ach_set_probe', 'ach_read_probe', 'ach_set_probe_range', 'ach_read_probe_slot', 'ach_bench_gemm', 'ach_set_option', 'ach_get_option', 'ach_option_key', 'ach_preprocess_radar',
-               'ach_normalize_points', 'ach_preprocess_image', 'ach_seg_argmax', 'ach_seg_resize_argmax', 'ach_correct_boxes', 'ach_train_pn2_fps', 'ach_train_pn2_group', 'ach_train_pn2_group_bwd', 'ach_train_pn2_interp', 'ach_train_gemm', 'ach_train_gemm_p', 'ach_train_set_gemm_precision', 'ach_train_get_gemm_precision', 'ach_train_bn_stats', 'ach_train_bn_running', 'ach_train_bn_relu_fwd', 'ach_train_bn_relu_bwd', 'ach_train_dw3x3', 'ach_train_dw3x3_wgrad', 'ach_train_max_points', 'ach_train_log_softmax', 'ach_resample_pass_u8', 'ach_train_act', 'ach_train_mul', 'ach_train_layernorm', 'ach_train_layernorm_bwd', 'ach_train_dwconv', 'ach_train_dwconv_wgrad',
-               'ach_train_im2col', 'ach_train_softmax', 'ach_train_upsample2x', 'ach_train_maxpool', 'ach_train_avgpool3', 'ach_train_row_reduce', 'ach_train_row_scale',
-               'ach_train_col_reduce', 'ach_train_col_scale', 'ach_train_instnorm', 'ach_train_l2norm', 'ach_train_deform_im2col', 'ach_train_deform_bwd',
-               'ach_record_words', 'ach_all_gather_records', 'ach_count_saturated', 'ach_train_yolo_loss', 'ach_train_loss_scale', 'ach_train_seg_loss',
-               'ach_eval_confusion', 'ach_eval_match', 'ach_data_letterbox_batch', 'ach_data_labels_batch', 'ach_data_radar_maps', 'ach_data_radar_points', 'ach_seg_overlay_frames', 'ach_correct_boxes_frames', 'ach_draw_detections_frames')
+    """dlopen + prototypes for every symbol declared in include/achelous.h, derived from the header itself (parse_header)."""
+    SYMBOLS = tuple(PROTOTYPES)
 
     def __init__(self, path):
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: build it with `make -C achelous_amd/csrc` "
                                f"(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         self.path = path
-        self.lib = L = ctypes.CDLL(path)
-        vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t, ctypes.c_float
-        L.ach_create.argtypes = [ctypes.POINTER(AchConfig), ctypes.POINTER(vp)]
-        L.ach_create.restype = ctypes.c_int
-        L.ach_destroy.argtypes = [vp]
-        L.ach_destroy.restype = None
-        L.ach_last_error.argtypes = [vp]
-        L.ach_last_error.restype = ctypes.c_char_p
-        L.ach_load_weights.argtypes = [vp, ctypes.POINTER(AchTensorDesc), sz]
-        L.ach_load_weights.restype = ctypes.c_int
-        L.ach_set_option.argtypes = [vp, ctypes.c_char_p, i32]
-        L.ach_set_option.restype = ctypes.c_int
-        # (the two option queries are bound where the library exports them: the co-residency tests also load tests/variants libraries that were built
-        #  before these entries existed; tests/test_abi_and_host.py holds the product to every declared symbol, and get_option on a library without them raises)
-        if hasattr(L, 'ach_get_option'):
-            L.ach_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
-            L.ach_get_option.restype = ctypes.c_int
-        if hasattr(L, 'ach_option_key'):
-            L.ach_option_key.argtypes = [i32]
-            L.ach_option_key.restype = ctypes.c_char_p
-        L.ach_plan.argtypes = [vp, i32]
-        L.ach_plan.restype = ctypes.c_int
-        L.ach_arena_bytes.argtypes = [vp]
-        L.ach_arena_bytes.restype = sz
-        L.ach_forward.argtypes = [vp] + [vp] * 9 + [vp]
-        L.ach_forward.restype = ctypes.c_int
-        L.ach_forward_detect.argtypes = [vp] + [vp] * 9 + [vp, f32, f32, i32, vp, vp, vp, vp, vp]
-        L.ach_forward_detect.restype = ctypes.c_int
-        L.ach_join.argtypes = [vp, vp]
-        L.ach_join.restype = ctypes.c_int
-        L.ach_forwards_in_flight.argtypes = [vp]
-        L.ach_forwards_in_flight.restype = ctypes.c_int
-        L.ach_decode.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-        L.ach_decode.restype = ctypes.c_int
-        L.ach_nms_workspace_bytes.argtypes = [vp, i32]
-        L.ach_nms_workspace_bytes.restype = sz
-        L.ach_nms.argtypes = [vp, i32, vp, f32, f32, i32, vp, vp, vp, vp, vp]
-        L.ach_nms.restype = ctypes.c_int
-        L.ach_preprocess_radar.argtypes = [vp, i32, i32, vp, vp, vp]
-        L.ach_preprocess_radar.restype = ctypes.c_int
-        L.ach_normalize_points.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-        L.ach_normalize_points.restype = ctypes.c_int
-        L.ach_preprocess_image.argtypes = [vp, i32, vp, vp, vp]
-        L.ach_preprocess_image.restype = ctypes.c_int
-        L.ach_seg_argmax.argtypes = [vp, i32, i32, vp, vp, vp]
-        L.ach_seg_argmax.restype = ctypes.c_int
-        L.ach_seg_resize_argmax.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp]
-        L.ach_seg_resize_argmax.restype = ctypes.c_int
-        L.ach_correct_boxes.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]
-        L.ach_correct_boxes.restype = ctypes.c_int
-        i64 = ctypes.c_int64
-        L.ach_train_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp]
-        L.ach_train_gemm.restype = ctypes.c_int
-        L.ach_train_gemm_p.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]
-        L.ach_train_gemm_p.restype = ctypes.c_int
-        L.ach_train_pn2_fps.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-        L.ach_train_pn2_group.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]
-        L.ach_train_pn2_group_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.ach_train_pn2_interp.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
-        for f in (L.ach_train_pn2_fps, L.ach_train_pn2_group, L.ach_train_pn2_group_bwd, L.ach_train_pn2_interp):
-            f.restype = ctypes.c_int
-        L.ach_train_bn_running.argtypes = [vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, vp]
-        L.ach_train_bn_running.restype = ctypes.c_int
-        L.ach_train_set_gemm_precision.argtypes = [i32]
-        L.ach_train_set_gemm_precision.restype = ctypes.c_int
-        L.ach_train_get_gemm_precision.argtypes = []
-        L.ach_train_get_gemm_precision.restype = ctypes.c_int
-        L.ach_train_bn_stats.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-        L.ach_train_bn_stats.restype = ctypes.c_int
-        L.ach_train_bn_relu_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]
-        L.ach_train_bn_relu_fwd.restype = ctypes.c_int
-        L.ach_train_bn_relu_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]
-        L.ach_train_bn_relu_bwd.restype = ctypes.c_int
-        L.ach_train_max_points.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
-        L.ach_train_max_points.restype = ctypes.c_int
-        L.ach_train_log_softmax.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-        L.ach_train_log_softmax.restype = ctypes.c_int
-        L.ach_train_dw3x3.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.ach_train_dw3x3.restype = ctypes.c_int
-        L.ach_train_dw3x3_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-        L.ach_train_dw3x3_wgrad.restype = ctypes.c_int
-        for name, args in (('ach_resample_pass_u8', [vp, vp, vp, vp] + [i32] * 7 + [i64, i64, vp]),
-                           ('ach_train_act', [vp, vp, vp, i64, i32, vp]),
-                           ('ach_train_mul', [vp, vp, vp, i64, vp]),
-                           ('ach_train_layernorm', [vp, vp, vp, vp, vp, vp, i64, i32, i64, f32, vp]),
-                           ('ach_train_layernorm_bwd', [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp]),
-                           ('ach_train_dwconv', [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-                           ('ach_train_dwconv_wgrad', [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-                           ('ach_train_im2col', [vp, vp] + [i32] * 13 + [vp]),
-                           ('ach_train_softmax', [vp, vp, vp, vp, i64, i32, vp]),
-                           ('ach_train_upsample2x', [vp, vp, i64, i32, i32, i32, vp]),
-                           ('ach_train_maxpool', [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
-                           ('ach_train_avgpool3', [vp, vp, i64, i32, i32, vp]),
-                           ('ach_train_row_reduce', [vp, vp, vp, i64, i64, f32, vp]),
-                           ('ach_train_row_scale', [vp, vp, vp, i64, i64, i64, vp]),
-                           ('ach_train_col_reduce', [vp, vp, vp, i64, i64, f32, vp]),
-                           ('ach_train_col_scale', [vp, vp, vp, i64, i64, vp]),
-                           ('ach_train_instnorm', [vp] * 10 + [i64, i64, i32, f32, vp]),
-                           ('ach_train_l2norm', [vp, vp, vp, vp, vp, i64, i64, f32, vp]),
-                           ('ach_train_deform_im2col', [vp, vp, vp, vp] + [i32] * 8 + [vp]),
-                           ('ach_train_deform_bwd', [vp] * 7 + [i32] * 8 + [vp]),
-                           ('ach_train_yolo_loss', [vp] * 5 + [i32] * 9 + [f32] * 3 + [vp] * 10),
-                           ('ach_train_loss_scale', [vp, vp, vp, i64, vp]),
-                           ('ach_train_seg_loss', [vp, vp, i32, vp, i32, i32, i64, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
-                           ('ach_eval_confusion', [vp, i32, i32, vp, i32, i32, i32, i64, vp, vp]),
-                           ('ach_eval_match', [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
-                           ('ach_data_letterbox_batch', [vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, i64, vp, i32, vp]),
-                           ('ach_data_labels_batch', [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]),
-                           ('ach_data_radar_maps', [vp, i64, i32, vp, vp, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp, i64, vp, i32, vp]),
-                           ('ach_data_radar_points', [vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
-                           ('ach_seg_overlay_frames', [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, i64, vp, i64, vp, i64, vp]),
-                           ('ach_correct_boxes_frames', [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]),
-                           ('ach_draw_detections_frames', [vp, i64, vp, vp, i32, vp, vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp])):
-            getattr(L, name).argtypes = args
-            getattr(L, name).restype = ctypes.c_int
-        L.ach_record_words.argtypes = [i32, i32]
-        L.ach_record_words.restype = sz
-        L.ach_all_gather_records.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-        L.ach_all_gather_records.restype = ctypes.c_int
-        L.ach_count_saturated.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.ach_count_saturated.restype = ctypes.c_int
-        L.ach_tap_count.argtypes = [vp]
-        L.ach_tap_count.restype = ctypes.c_int
-        L.ach_tap_name.argtypes = [vp, ctypes.c_int]
-        L.ach_tap_name.restype = ctypes.c_char_p
-        L.ach_tap_shape.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
-        L.ach_tap_shape.restype = ctypes.c_int
-        L.ach_read_tap.argtypes = [vp, ctypes.c_char_p, vp, sz]
-        L.ach_read_tap.restype = ctypes.c_int
-        L.ach_plan_launches.argtypes = [vp]
-        L.ach_plan_launches.restype = ctypes.c_int
-        L.ach_op_name.argtypes = [vp, ctypes.c_int]
-        L.ach_op_name.restype = ctypes.c_char_p
-        L.ach_op_bytes.argtypes = [vp, ctypes.c_int]
-        L.ach_op_bytes.restype = ctypes.c_double
-        L.ach_op_flops.argtypes = [vp, ctypes.c_int]
-        L.ach_op_flops.restype = ctypes.c_double
-        L.ach_op_layout_bytes.argtypes = [vp, ctypes.c_int]
-        L.ach_op_layout_bytes.restype = ctypes.c_double
-        L.ach_op_stream.argtypes = [vp, ctypes.c_int]
-        L.ach_op_stream.restype = ctypes.c_int
-        L.ach_forward_profiled.argtypes = [vp] + [vp] * 9 + [vp, vp, sz]
-        L.ach_forward_profiled.restype = ctypes.c_int
-        L.ach_set_probe.argtypes = [vp, ctypes.c_int]
-        L.ach_set_probe.restype = ctypes.c_int
-        L.ach_read_probe.argtypes = [vp, ctypes.POINTER(f32), ctypes.POINTER(ctypes.c_int)]
-        L.ach_read_probe.restype = ctypes.c_int
-        L.ach_set_probe_range.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.ach_set_probe_range.restype = ctypes.c_int
-        L.ach_read_probe_slot.argtypes = [vp, ctypes.c_int, ctypes.POINTER(f32), ctypes.POINTER(ctypes.c_int)]
-        L.ach_read_probe_slot.restype = ctypes.c_int
-        L.ach_bench_gemm.argtypes = [vp] + [ctypes.c_int] * 8 + [vp, ctypes.POINTER(f32)]
-        L.ach_bench_gemm.restype = ctypes.c_int
+        self.lib = ctypes.CDLL(path)
+        # (an entry is bound where the library exports it: the co-residency tests also load libraries built from older sources; tests/test_abi_and_host.py
+        #  holds the product to every declared symbol, and calling an entry a library lacks raises AttributeError)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(self.lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
 
 
 _hip_library = None

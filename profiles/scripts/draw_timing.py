@@ -7,7 +7,7 @@ reference's thickness 9 and font size 32).
   c   for scale: the overlay launch (`seg_maps_frames`, two softmax launches + one launch), whose code this change does not touch
 Device events around the calls (b: a host clock around work that ends in a synchronise), warm-up, >= 0.3 s of timed work per leg and round, legs alternated in one
 process, median and spread of the rounds.  Before anything is timed, leg a's bytes are compared with leg b's on the first frames.
-`--lib PATH`: a library built with another tile shape (hipcc ... -DACH_DRAW_TX=16 | 32 | 64 on csrc/api.cpp: 64 x 16, 128 x 8, 256 x 4 pixels; default 8: 32 x 32);
+`--lib PATH`: a library built with another tile shape (hipcc ... -DACH_DRAW_TX=16 | 32 | 64 on csrc/api_frames.cpp: 64 x 16, 128 x 8, 256 x 4 pixels; default 8: 32 x 32);
 name the file after its tile, the name is the leg's label.
 Needs PIL with FreeType.  usage: python profiles/scripts/draw_timing.py [--batch 64] [--rounds 5] [--out FILE] [--lib PATH ...]"""
 import argparse

@@ -43,6 +43,75 @@ def test_hip_library_exports_every_declared_symbol():
         raise eng_mod._ERRORS[rc](L.lib.ach_last_error(None).decode())
 
 
+def _declared_parameter_counts():
+    """{entry: number of parameters} read from the header by this file's own pattern, not by the parser under test"""
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'achelous.h')).read(), flags=re.S)
+    return {name: 0 if args.strip() == 'void' else args.count(',') + 1 for name, args in re.findall(r'\b(ach_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src)}
+
+
+def test_bindings_derived_from_the_header_have_the_declared_signatures():
+    """The prototypes come from include/achelous.h (engine.parse_header).  A few spelled out, covering between them every scalar type, both return types that are not
+    int, the array parameter and the empty parameter list; and every declared entry is bound on a loaded library with the header's number of parameters."""
+    from emu_util import emu_library
+    vp, cp, i32, i64, sz, f32, f64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
+    literal = {
+        'ach_create': (ctypes.c_int, [vp, vp]),
+        'ach_destroy': (None, [vp]),
+        'ach_last_error': (cp, [vp]),
+        'ach_arena_bytes': (sz, [vp]),
+        'ach_option_key': (cp, [i32]),
+        'ach_train_get_gemm_precision': (ctypes.c_int, []),
+        'ach_train_gemm_p': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]),
+        'ach_train_bn_running': (ctypes.c_int, [vp, vp, vp, vp, i32, f32, f32, vp]),
+        'ach_data_radar_maps': (ctypes.c_int, [vp, i64, i32, vp, vp, i32, i32, f64, f64, vp, vp, i64, vp, i32, vp]),
+        'ach_tap_shape': (ctypes.c_int, [vp, cp, vp, vp]),
+        'ach_op_bytes': (f64, [vp, ctypes.c_int]),
+    }
+    for name, (restype, argtypes) in literal.items():
+        assert eng_mod.PROTOTYPES[name] == (restype, argtypes), name
+    counts = _declared_parameter_counts()
+    assert list(eng_mod.NativeLibrary.SYMBOLS) == list(eng_mod.PROTOTYPES) and set(counts) == set(eng_mod.PROTOTYPES) and len(counts) == 89
+    L = emu_library().lib
+    for name, n in counts.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+        assert fn.restype is eng_mod.PROTOTYPES[name][0] and list(fn.argtypes) == eng_mod.PROTOTYPES[name][1], name
+
+
+@pytest.mark.parametrize('text', ['int ach_bad(uint8_t value);', 'int ach_bad(const ach_config cfg);', 'long ach_bad(int32_t value);', 'int ach_bad(int32_t);'])
+def test_a_header_line_the_parser_cannot_type_raises(text):
+    """an unknown scalar, a struct by value, an unknown return type, a parameter without a name: never a default"""
+    good = 'int ach_good(const float* x, int64_t n);\n'
+    assert eng_mod.parse_header(good) == {'ach_good': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64])}
+    with pytest.raises(ValueError):
+        eng_mod.parse_header(good + text)
+
+
+def _product_library():
+    if not os.path.exists(eng_mod.HIP_LIBRARY):
+        import __graft_entry__
+        __graft_entry__.build()
+    return eng_mod.NativeLibrary(eng_mod.HIP_LIBRARY)
+
+
+@pytest.mark.parametrize('which', ['emulation', 'product'])
+def test_entries_without_a_handle_share_one_error_text(which):
+    """ach_last_error(NULL) is one per-thread text behind the three files of the C boundary (api.cpp, api_train.cpp, api_frames.cpp): a failing call of each leaves its
+    own message there, whatever failed before.  Every call here is rejected by its argument check, before any device call, so the product library runs host-only."""
+    from emu_util import emu_library
+    L = (emu_library() if which == 'emulation' else _product_library()).lib
+    cfg, h = eng_mod.AchConfig(7, 9, 0, 5, 320, 5, 8, 512, 1, 1, 0, 0, 0), ctypes.c_void_p()          # backbone id 5: not 'en' / 'mv'
+    null = ctypes.c_void_p()
+    one = ctypes.c_void_p(64)                                                                           # a non-null address nothing reads
+    calls = [(lambda: L.ach_create(ctypes.byref(cfg), ctypes.byref(h)), -2, b"backbone must be 'en' or 'mv'"),
+             (lambda: L.ach_train_mul(one, one, one, 0, null), -1, b'bad arguments: ach_train_mul'),
+             (lambda: L.ach_resample_pass_u8(null, null, null, null, 1, 1, 1, 1, 1, 3, 0, 3, 3, null), -1, b'bad resample_pass arguments'),
+             (lambda: L.ach_data_labels_batch(one, 0, one, one, one, one, 0, 0, 8, 9, one, one, 0, null), -1, b'bad arguments: ach_data_labels_batch')]
+    for call, code, text in calls + calls[::-1]:
+        assert call() == code and L.ach_last_error(None) == text, text
+    assert not h.value
+
+
 @pytest.mark.parametrize('name', ['en_s0', 'en_s2', 'mv_s2', 'en_s0_cdf', 'en_s1'])
 def test_state_dict_contract(name):
     meta = json.load(open(os.path.join(REPO, 'tests', 'golden', name + '.keys.json')))

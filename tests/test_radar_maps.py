@@ -190,7 +190,7 @@ def test_points_and_labels(dev, kind):
 
 
 def test_entry_calls_do_not_grow_with_the_batch(dev, monkeypatch):
-    """one call of each C entry per batch (one launch for the raw map, two for the normalised one, one for the points: api.cpp), at B = 1 and B = 4"""
+    """one call of each C entry per batch (one launch for the raw map, two for the normalised one, one for the points: api_frames.cpp), at B = 1 and B = 4"""
     lib = train_ops._lib(torch.empty(1, device=dev))
     calls = {}
     for sym in ('ach_data_radar_maps', 'ach_data_radar_points', 'ach_preprocess_radar', 'ach_normalize_points'):

@@ -236,7 +236,7 @@ def _cases(dev):
     yield 'batchnorm+relu', lambda: _check(lambda x, g, b: TF.batchnorm(x, g, b, None, None, True, 0.1, 1e-5, True),
                                            lambda x, g, b: torch.relu(F.batch_norm(x, None, None, g, b, True, 0.1, 1e-5)),
                                            [(_r(4, 6, 5, 7), True), (_r(6, seed=1) + 1, True), (_r(6, seed=2), True)], dev)
-    # ---- the shapes at which a 320 x 320 training step dispatches differently (api.cpp: train_slices, the finalize kernels, the scalar / four-per-thread forms)
+    # ---- the shapes at which a 320 x 320 training step dispatches differently (api_train.cpp: train_slices, the finalize kernels, the scalar / four-per-thread forms)
     for shape in ((8, 32, 80, 80), (32, 32, 80, 80), (32, 48, 40, 40)):            # parameter gradients in 4 / 13 / 4 slices + train_ln_bwd_param_finalize_kernel
         yield _ln_case(dev, f'layernorm_channels {shape}', shape)
     for shape in ((11, 5, 320, 320), (8, 16, 320, 320)):                           # 64 slices (the clamp) / 50 slices

@@ -130,7 +130,7 @@ def _oracle_training_reference(sd, kw, x, xr, xp, cot, dtype=torch.float64):
 
 
 ORACLE_CASES = [('S2', True, 64, 'en_s2'), ('S0', False, 64, 'en_s0'), ('S2', True, 64, 'mv_s2'), ('S0', True, 64, 'en_s0_cdf'), ('S0', True, 320, 'en_s0')]
-# The 320 px case is one whole step at the size training runs at, where api.cpp dispatches the sliced reductions, split-K and the four-per-thread kernels.  Batch 4, not 2:
+# The 320 px case is one whole step at the size training runs at, where api_train.cpp dispatches the sliced reductions, split-K and the four-per-thread kernels.  Batch 4, not 2:
 # PointNet's STN normalises its fc layers over the batch, and at 2 samples torch's own float32 is 50 % off the float64 truth.  At this size the step is well enough
 # conditioned to be held to the yardstick alone (`strict`): outputs and gradients within 6 x torch-float32's own error, no 6e-2 floor.  Measured under the emulation:
 # outputs 6e-6 to 2e-5 (torch float32: 7e-6 to 1e-3), median gradient error 4e-3 (1.5e-2), worst ratio to the yardstick over the 527 gradients 2.6.

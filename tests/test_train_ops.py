@@ -328,3 +328,45 @@ def test_pointnet_seg_state_dict_is_the_reference_pc_seg_model():
     ref = [(k[len('pc_seg_model.'):], tuple(s)) for k, s, _ in meta['keys'] if k.startswith('pc_seg_model.')]
     mine = [(k, tuple(v.shape)) for k, v in train_ops.PointNetSeg(8, 5).state_dict().items()]
     assert len(ref) == 118 and ref == mine
+
+
+# ---------------------------------------------------------------------------------------- both sides of every shape-dependent dispatch of the C entries
+def _dispatch_cases(dev):
+    """The smallest shapes on either side of the predicates the C entries (csrc/api_train.cpp) choose a kernel by, each against torch autograd with the check and the
+    bounds of tests/test_train_functional.py (`_check`: float64 truth, float32 yardstick, 2e-4 at most):
+      four elements per thread or one — a count that divides by four on 16-byte aligned pointers, a count that does not, and the aligned count on a view one float in;
+      depthwise k = 3 / 5 / 7 / 9 (unrolled) and 11 (the generic kernels, forward and weight gradient) on a row of 8 (four outputs per thread) and of 6 (one);
+      a per-channel reduction in one slice and, above 32 768 values per channel, in two: BatchNorm, LayerNorm's parameter gradients, the depthwise weight gradient."""
+    import torch.nn.functional as F
+    import test_train_functional as P
+    from achelous_amd import train_functional as TF
+    one_in = lambda f: (lambda x: f(torch.cat([x.new_zeros(1), x.reshape(-1)])[1:].view(x.shape)))          # the same values, 4 bytes past a 16-byte boundary
+    for name, n, wrap in (('n=8', 8, lambda f: f), ('n=6', 6, lambda f: f), ('n=8 one float in', 8, one_in)):
+        yield f'act {name}', (lambda n=n, wrap=wrap: P._check(wrap(lambda x: TF.act(x, TF.ACT_SILU)), F.silu, [(P._r(n, scale=2), True)], dev))
+    for k in (3, 5, 7, 9, 11):
+        for W in (8, 6):
+            yield f'dwconv k{k} W{W}', (lambda k=k, W=W: P._check(TF.dwconv, P._ref_dw, [(P._r(1, 2, 5, W), True), (P._r(2, 1, k, k, seed=1, scale=0.3), True), (P._r(2, seed=2), True)], dev))
+    for hw in (8, 128):
+        shape = (2, 2, hw, hw)
+        yield f'batchnorm {shape}', (lambda shape=shape: P._check(lambda x, g, b: TF.batchnorm(x, g, b, None, None, True, 0.1, 1e-5, False), P._ref_bn, [(P._r(*shape), True)] + P._affine(2), dev))
+        yield f'layernorm {shape}', (lambda shape=shape: P._check(lambda x, g, b: TF.layernorm_channels(x, g, b, 1e-6), P._ref_ln, [(P._r(*shape), True)] + P._affine(2), dev))
+        yield f'dwconv k3 {shape}', (lambda shape=shape: P._check(TF.dwconv, P._ref_dw, [(P._r(*shape), True), (P._r(2, 1, 3, 3, seed=1, scale=0.3), True), (P._r(2, seed=2), True)], dev))
+
+
+DISPATCH_NAMES = [n for n, _ in _dispatch_cases('cpu')]
+
+
+@pytest.mark.parametrize('name', DISPATCH_NAMES)
+def test_emulated_dispatch_sides_match_autograd(name):
+    from emu_util import emu_library
+    train_ops._lib.test_library = emu_library()
+    try:
+        dict(_dispatch_cases('cpu'))[name]()
+    finally:
+        train_ops._lib.test_library = None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', DISPATCH_NAMES)
+def test_gpu_dispatch_sides_match_autograd(name):
+    dict(_dispatch_cases('cuda'))[name]()
