@@ -215,6 +215,10 @@ const char* ach_op_name(const ach_handle* h, int i) { const ach::Op* op = op_at(
 double ach_op_bytes(const ach_handle* h, int i) { const ach::Op* op = op_at(h, i); return op ? op->bytes : 0; }
 double ach_op_layout_bytes(const ach_handle* h, int i) { const ach::Op* op = op_at(h, i); return op ? op->layout_bytes : 0; }
 int ach_op_stream(const ach_handle* h, int i) { const ach::Op* op = op_at(h, i); return op ? op->stream : -1; }
+int ach_op_sync(const ach_handle* h, int i, int* wait, int* signal, int* xwait, int* xsignal) {
+    const ach::Op* op = op_at(h, i);
+    return (op && wait && signal && xwait && xsignal) ? (*wait = op->wait, *signal = op->signal, *xwait = op->xwait, *xsignal = op->xsignal, ACH_OK) : ACH_ERR_INVALID;
+}
 double ach_op_flops(const ach_handle* h, int i) { const ach::Op* op = op_at(h, i); return op ? op->flops : 0; }
 int ach_forward_profiled(ach_handle* h, const void* image, const void* radar, const void* points, void* det3, void* det4,
                          void* det5, void* se_seg, void* lane_seg, void* pc_seg, void* stream, float* op_ms, size_t capacity) {

@@ -108,7 +108,7 @@ void EngineBase::invalidate_plan() {
 }
 void EngineBase::reset_plan(int B) {
     invalidate_plan(); batch = B;
-    cur_stream = 0; pending_wait = -1; pending_wait2 = -1; pending_xwait = 0;
+    cur_stream = 0; pending = {};
     t_regions.clear(); sat_dev_regions = 0;
     warena_used = 0; aarena_used = 0;
 }
@@ -184,11 +184,9 @@ void EngineBase::ensure_streams() {
 //
 // Pipelined mode (option "pipeline"): the end-of-forward join is left to join(), so that the caller can enqueue forward k+1 before
 // forward k's side streams have finished — the caller's stream is free after the neck and starts the next backbone while stream 2
-// still runs forward k's decoders, fusion, head, decode and NMS.  Buffers are NOT double-buffered; the two places where forward k+1
-// overwrites something forward k's stream 2 still reads are ordered by a cross-forward event instead: the FPN outputs / attention
-// maps (written by the neck on the caller's stream) and the radar pyramid (written by stream 1) are last read by the fusion launch
-// of forward k (`xsignal`), and the first neck launch / first radar launch of forward k+1 (`xwait`) wait for it.  Everything else a
-// stream rewrites is only read by itself (in order) or by launches that the in-forward join events already order.
+// still runs forward k's decoders, fusion, head, decode and NMS.  Buffers are NOT double-buffered: where forward k+1 overwrites something
+// forward k still reads, a cross-forward event orders the two (XDep, engine_schedule.h).  Everything else a stream rewrites is only read
+// by itself (in order) or by launches that the in-forward join events already order.
 // At most two forwards may be un-joined: the third call joins the oldest on its own stream first.
 void EngineBase::join(hipStream_t s) {
     if (joined >= issued) return;
@@ -216,8 +214,7 @@ void EngineBase::run_eager(hipStream_t s) {
         Op& op = ops[i];
         hipStream_t st = s;
         if (multi && op.stream > 0) { st = side_stream[op.stream - 1]; used[op.stream - 1] = true; }
-        if (multi && op.wait_ev >= 0) (void)hipStreamWaitEvent(st, ev_join[op.wait_ev], 0);
-        if (multi && op.wait_ev2 >= 0) (void)hipStreamWaitEvent(st, ev_join[op.wait_ev2], 0);
+        if (multi) for (unsigned d = 0, w = op.wait; w; ++d, w >>= 1) if (w & 1) (void)hipStreamWaitEvent(st, ev_join[d], 0);     // (the lower event first)
         if (piped && issued > 0) {
             unsigned w = op.xwait;
             if (dbg_xwait2_op >= 0) w = (w & ~(1u << kXDecoders)) | (int(i) == dbg_xwait2_op ? 1u << kXDecoders : 0u);
@@ -226,10 +223,10 @@ void EngineBase::run_eager(hipStream_t s) {
         for (auto& pr : probes) if (int(i) == pr.first) (void)hipEventRecord(pr.ev0[size_t(pr.count % kProbeEvents)], st);
         op.fn(st);
         for (auto& pr : probes) if (int(i) == pr.last) { (void)hipEventRecord(pr.ev1[size_t(pr.count % kProbeEvents)], st); ++pr.count; }
-        if (multi && op.signal_ev >= 0) (void)hipEventRecord(ev_join[op.signal_ev], st);
+        if (multi) for (unsigned d = 0, g = op.signal; g; ++d, g >>= 1) if (g & 1) (void)hipEventRecord(ev_join[d], st);
         if (piped) for (unsigned d = 0, g = op.xsignal; g; ++d, g >>= 1) if (g & 1) { (void)hipEventRecord(xdep[d].ev[par], st); xdep[d].recorded[par] = true; }
     }
-    if (detect_tail) detect_tail((multi && detect_stream > 0 && used[detect_stream - 1]) ? side_stream[detect_stream - 1] : s);   // det maps are final on that stream
+    if (detect_tail) detect_tail((multi && sched.detect_stream > 0 && used[sched.detect_stream - 1]) ? side_stream[sched.detect_stream - 1] : s);   // det maps are final on that stream
     if (piped) {
         for (int k = 0; k < kSideStreams; ++k) { done_used[par][k] = used[k]; if (used[k]) (void)hipEventRecord(ev_done[k][par], side_stream[k]); }
         ++issued;

@@ -11,6 +11,7 @@
 
 #include "../../include/achelous.h"
 #include "ach_platform.h"
+#include "engine_schedule.h"
 
 namespace ach {
 
@@ -35,15 +36,6 @@ struct TapInfo {
     int add_eye = 0;              // rows kind: add identity of this size (PointNet transforms are stored without +I)
 };
 
-// The cross-forward dependencies of the pipelined plan (option "pipeline"; run_eager in engine.cpp): buffers are not double-buffered, so forward k+1 may overwrite something
-// only after forward k has read it for the last time.  Each has a pair of alternating events; a launch carries one bit per dependency it waits for / signals.
-enum XDep {
-    kXFusion = 0,     // fusion's reads of the FPN outputs / attention maps and the radar pyramid: the first neck launch and the first radar launch of the next forward wait for this forward's fusion launch
-    kXDecoders = 1,   // the same for the DECODERS' reads of the attention maps: since fusion + head moved to the radar stream (head_stream = 0) the fusion launch no longer follows the decoders in stream order, so kXFusion alone would let the next forward's neck overwrite what this forward's decoders still read
-    kXNeck = 2,       // option dec_fork = 3 (the NECK on stream 2): the backbone launch that first writes a feature map the previous forward's neck reads (stage 1's output, a slice of the neck's concat buffer) waits for that neck's last reader of the backbone's maps
-    kXDeps = 3
-};
-
 struct Op {
     std::string name;
     std::function<void(hipStream_t)> fn;
@@ -51,11 +43,10 @@ struct Op {
     double layout_bytes = 0;      // the same count over the pixel pitches actually stored (channel padding included): what the launch must move
     double flops = 0;             // 2 * MACs of one launch (dense contractions only)
     int stream = 0;               // 0: caller's stream (image path) ; 1, 2: engine-owned side streams (radar / point branches)
-    int wait_ev = -1, wait_ev2 = -1;   // join: wait for these events before the launch
-    int signal_ev = -1;           // record this event after the launch
-    // pipelined forwards: one bit per cross-forward dependency (XDep).  `xwait`: the first launch of its stream to overwrite buffers that the PREVIOUS
-    // forward still reads through that dependency -> waits for that forward's `xsignal` launch, the last one that reads them.
-    unsigned char xwait = 0, xsignal = 0;
+    // joins inside the forward: one bit per JoinEvent the launch waits for before it starts / records behind it.  Pipelined forwards: one bit per cross-forward
+    // dependency (XDep).  `xwait`: the first launch of its stream to overwrite buffers that the PREVIOUS forward still reads through that dependency -> waits
+    // for that forward's `xsignal` launch, the last one that reads them.  (engine_schedule.h places all four)
+    unsigned char wait = 0, signal = 0, xwait = 0, xsignal = 0;
 };
 
 struct IoPtrs {
@@ -80,7 +71,6 @@ public:
 #define ACH_OPTION(key, type, member, def, rule, lo, hi) type member = def;
 #include "engine_options.h"
 #undef ACH_OPTION
-    int radar_start_eff() const { return radar_start == -2 ? ((pipeline && multi_stream) ? 2 : 1) : radar_start; }
     int batch = 0;
     std::vector<Op> ops;
     std::map<std::string, TapInfo> taps;
@@ -180,18 +170,20 @@ protected:
 #endif
         Op op{name, std::move(fn), bytes, layout_bytes < 0 ? bytes : layout_bytes, flops};
         op.stream = cur_stream;
-        op.wait_ev = pending_wait; op.wait_ev2 = pending_wait2;
-        pending_wait = -1; pending_wait2 = -1;
-        op.xwait = pending_xwait; pending_xwait = 0;
+        op.wait = pending.wait; op.xwait = pending.xwait;
+        pending = {};
         ops.push_back(std::move(op));
     }
     // branch bookkeeping while the plan is built
-    int cur_stream = 0, pending_wait = -1, pending_wait2 = -1;
-    int detect_stream = 1;            // the stream the detection head ends on (decode + NMS of ach_forward_detect follow it there)
-    void signal_after_last(int ev) { if (!measuring && !ops.empty()) ops.back().signal_ev = ev; }
-    void wait_before_next(int ev) { pending_wait = ev; }
-    void wait_before_next2(int ev) { pending_wait2 = ev; }
-    static constexpr int kSideStreams = 3, kJoinEvents = 4;
+    // the builder functions announce where they are; the schedule (engine_schedule.h, computed at the top of build()) says what that means: enter() — the launches
+    // that follow run on the segment's stream, the first of them behind the segment's waits; reached() — the last launch so far records the point's events
+    Schedule sched;
+    int cur_stream = 0;
+    Schedule::Marks pending;          // waits of the next launch
+    void wait_next(const Schedule::Marks& m) { pending.wait |= m.wait; pending.xwait |= m.xwait; }
+    void enter(Segment g) { cur_stream = sched.stream[g]; wait_next(sched.enter[g]); }
+    void reached(Point p) { wait_next(sched.at[p]); if (!measuring && !ops.empty()) { ops.back().signal |= sched.at[p].signal; ops.back().xsignal |= sched.at[p].xsignal; } }
+    static constexpr int kSideStreams = 3;
     hipStream_t side_stream[kSideStreams] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kJoinEvents] = {nullptr, nullptr, nullptr, nullptr}, ev_end[kSideStreams] = {nullptr, nullptr, nullptr};
     bool streams_ready = false;
@@ -202,9 +194,6 @@ protected:
     hipEvent_t ev_done[kSideStreams][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     bool done_used[2][kSideStreams] = {{false, false, false}, {false, false, false}};
     long issued = 0, joined = 0;
-    unsigned char pending_xwait = 0;
-    void mark_xwait_next(XDep d) { pending_xwait |= 1u << d; }
-    void mark_xsignal_last(XDep d) { if (!measuring && !ops.empty()) ops.back().xsignal |= 1u << d; }
 #if !defined(ACH_HOSTEMU)
     struct GraphEntry { IoPtrs io; hipGraphExec_t exec; unsigned long stamp; };
     std::vector<GraphEntry> graphs;

@@ -413,8 +413,8 @@ public:
                 size_t e = a + 1;
                 while (e < band_ops.size() && e - a < size_t(MLPB_RUN_MAX) && band_ops[e].op == band_ops[e - 1].op + 1 && band_ops[e].shape == band_ops[a].shape && band_ops[e].nb == band_ops[a].nb &&
                        band_ops[e].bp.m.X == band_ops[e - 1].bp.m.Y && band_ops[e].bp.bands == band_ops[a].bp.bands && band_ops[e].bp.rb == band_ops[a].bp.rb &&
-                       ops[band_ops[e].op].stream == ops[band_ops[a].op].stream && ops[band_ops[e].op].wait_ev < 0 && ops[band_ops[e].op].wait_ev2 < 0 && !ops[band_ops[e].op].xwait &&
-                       ops[band_ops[e - 1].op].signal_ev < 0 && !ops[band_ops[e - 1].op].xsignal) ++e;
+                       ops[band_ops[e].op].stream == ops[band_ops[a].op].stream && !ops[band_ops[e].op].wait && !ops[band_ops[e].op].xwait &&
+                       !ops[band_ops[e - 1].op].signal && !ops[band_ops[e - 1].op].xsignal) ++e;
                 const size_t n = e - a;
                 // (the bands of a frame must share an XCD — xcd_block: the launch's workgroups in eight equal chunks of whole frames — because the blocks hand their rows over through that L2)
                 const long nwg = long(band_ops[a].bp.bands) * band_ops[a].nb;
@@ -429,7 +429,7 @@ public:
                     const size_t first = band_ops[a].op, last = band_ops[e - 1].op;
                     Op& op = ops[first];
                     for (size_t k = first + 1; k <= last; ++k) { op.bytes += ops[k].bytes; op.layout_bytes += ops[k].layout_bytes; op.flops += ops[k].flops; }
-                    op.signal_ev = ops[last].signal_ev; op.xsignal = ops[last].xsignal;
+                    op.signal = ops[last].signal; op.xsignal = ops[last].xsignal;
                     op.name += "..+" + std::to_string(n - 1);
                     op.fn = [rp, nb, shape](hipStream_t s) mutable { launch_mlp_band_run<T>(rp, shape, nb, s); ++rp.epoch; };
                     ops.erase(ops.begin() + long(first) + 1, ops.begin() + long(last) + 1);
@@ -453,11 +453,10 @@ public:
     // When set, the next block output is written there instead of a fresh allocation (a channel slice of a concat buffer of the
     // neck: torch.cat((upsampled, backbone feature), 1) then needs no copy).  Consumed by the first block that produces an output.
     A preset_out; bool has_preset = false;
-    bool neck_on_side = false;        // this plan runs the neck on stream 2 (option dec_fork = 3; decided in build())
     A block_out(const A& like) {
         if (has_preset) {
             has_preset = false;
-            if (neck_on_side) mark_xwait_next(kXNeck);      // (the launch that writes this slice of the neck's concat buffer: the previous forward's neck, on stream 2, may still read it)
+            reached(kPtConcatSlice);            // (the neck on stream 2: the launch that writes this slice of the neck's concat buffer: the previous forward's neck, on stream 2, may still read it)
             if (preset_out.B != like.B || preset_out.H != like.H || preset_out.W != like.W || preset_out.C != like.C)
                 throw AchError{ACH_ERR_INVALID, "preset block output does not match the block"};
             return preset_out;
@@ -889,7 +888,7 @@ public:
             if (has_preset) throw AchError{ACH_ERR_INVALID, "stage output destination was not consumed"};
             feats[i] = x;
             merge_band_runs();
-            if (i == radar_start_eff()) signal_after_last(0);
+            reached(Point(kPtStage0 + i));
         }
     }
 
@@ -1043,15 +1042,15 @@ public:
         x = mv2block(pfx + ".mv2.2", x, 1, mc.ch[3]);
         x = mv2block(pfx + ".mv2.3", x, 1, mc.ch[3]);
         feats[0] = x;
-        if (radar_start_eff() == 0) signal_after_last(0);
+        reached(kPtStage0);
         x = mv2block(pfx + ".mv2.4", x, 2, mc.ch[4]);
         x = mvit_block(pfx + ".mvit.0", x, 2);
         feats[1] = x;
-        if (radar_start_eff() == 1) signal_after_last(0);
+        reached(kPtStage1);
         x = mv2block(pfx + ".mv2.5", x, 2, mc.ch[6]);
         x = mvit_block(pfx + ".mvit.1", x, 4);
         feats[2] = x;
-        if (radar_start_eff() >= 2) signal_after_last(0);
+        reached(kPtStage2);
         x = mv2block(pfx + ".mv2.6", x, 2, mc.ch[8]);
         x = mvit_block(pfx + ".mvit.2", x, 3);
         feats[3] = mv_conv(pfx + ".conv2", x, 1, 1);
@@ -1550,14 +1549,7 @@ public:
         // SPP (spp.py:41-67)
         const int c_ = w[3] / 2;
         if (c_ % 4) throw AchError{ACH_ERR_UNSUPPORTED, "SPP hidden width must be a multiple of 4"};
-        if (neck_on_side) {              // dec_fork = 3: everything from here on runs on stream 2, behind the backbone's last launch
-            if (measuring || ops.empty() || ops.back().signal_ev >= 0) { if (!measuring) throw AchError{ACH_ERR_INVALID, "dec_fork = 3: the backbone's last launch already signals an event"}; }
-            else ops.back().signal_ev = 2;
-            cur_stream = 2;
-            wait_before_next(2);
-        }
-        mark_xwait_next(kXFusion);       // pipelined forwards: the neck rewrites what the previous forward's stream 2 reads (engine.cpp)
-        mark_xwait_next(kXDecoders);     // ... and what its decoders read
+        reached(kPtBackboneEnd); enter(kSegNeck);
         A p5;
         bool spp_done = false;
         if constexpr (H16E) if (ghost_fuse && !full_taps && spp_fused_supported(m5.H, m5.W, w[3], c_) && m5.ld % 8 == 0) {
@@ -1599,13 +1591,7 @@ public:
         if (m3.p != c3.slice(w[1], w[1]).p) copy(f + ".cat3", m3, c3.slice(w[1], w[1]));
         A p3 = csp ? csp_layer(f + ".ghost_4_to_3", c3, w[1]) : ghost_bottleneck(f + ".ghost_4_to_3", c3, w[1]);
         tap("fpn4", p4); tap("fpn3", p3);
-        const bool split_dec = split_decoders != 0;
-        const bool piped = pipeline && multi_stream && !split_dec;
-        // option "dec_fork": where the pipelined plan's decoders leave the caller's stream — 0: behind the shared ShuffleAttention stage (round 3), 1: in front of it
-        // (the stage's three launches move to stream 2: the caller's stream is the pipelined loop's bottleneck), 2: as soon as p3 exists (the residual
-        // adds stay on the caller's stream and run beside the attention stage)
-        const int fork = neck_on_side ? 3 : (piped ? std::min(dec_fork, 2) : 0);
-        if (fork == 2) signal_after_last(2);
+        reached(kPtP3); enter(kSegResidual);
         // residual FPN outputs (ghostdualfpn.py:200) — computed BEFORE the decoders so that the detection branch (fusion + head,
         // on the radar stream) can start while the two heavy decoders still run on this stream
         q[0] = alloc(p3.B, p3.H, p3.W, p3.C);
@@ -1623,25 +1609,16 @@ public:
             const dim3 grid(unsigned(cdivl(mx, 256)), 3), block(256);
             add_op(f + ".q3+q4+q5", [aj, grid, block](hipStream_t s) { ACH_LAUNCH(add_multi_kernel<T>, grid, block, s, aj); }, bytes);
         }
-        signal_after_last(1);
-        if (fork == 3) mark_xsignal_last(kXNeck);        // the residual adds are the neck's last reader of the backbone's feature maps
+        reached(kPtFpnOutputs);
         // two segmentation decoders
         const char* names[2] = {"lane", "se"};
         const char* sa[2] = {"stage_3_lane_seg", "stage_3_semantic_seg"};
         const int oups[2] = {2, cfg.num_seg};
         void** outs[2] = {&io.lane, &io.se};
         A ysa[2];
-        if (fork == 1) { cur_stream = 2; wait_before_next(1); }                        // (event 1 = the residual adds, the caller's last launch of this forward)
-        if (fork == 2) { cur_stream = 2; wait_before_next(2); }
-        shuffle_attention_pair(f + "." + sa[0], f + "." + sa[1], p3, ysa[0], ysa[1]);
-        if (piped && fork == 0) { signal_after_last(2); cur_stream = 2; wait_before_next(2); }     // both decoders leave the caller's stream
-        if (split_dec) signal_after_last(2);   // the semantic decoder may start on its own stream
+        enter(kSegAttention); shuffle_attention_pair(f + "." + sa[0], f + "." + sa[1], p3, ysa[0], ysa[1]); reached(kPtAttention);
         for (int d = 0; d < 2; ++d) {
-            // past the shared attention stage the two decoders are independent: water-line decoder on the caller's stream, semantic
-            // decoder on stream 3 when the option is 1; option 2: the (shorter) water-line decoder joins side stream 1 behind the radar
-            // branch instead — no extra stream — and the semantic decoder keeps the caller's
-            if (split_decoders == 1 && d == 1) { cur_stream = 3; wait_before_next(2); }
-            if (split_decoders == 2) { cur_stream = d == 0 ? 1 : 0; if (d == 0) wait_before_next(2); }
+            enter(d == 0 ? kSegLaneDecoder : kSegSeDecoder);      // past the shared attention stage the two decoders are independent
             const std::string n = names[d];
             A y = ysa[d];
             tap(n + ".sa", y);
@@ -1679,8 +1656,7 @@ public:
             }
             decoder_last_level(up_of(2), gh_of(2), f + "." + n + "_seg_head", n + "." + lv[2], have_t ? t : y, cw[2], oups[d], outs[d], have_t ? &t : nullptr);
         }
-        if (piped) mark_xsignal_last(kXDecoders);    // the decoders' last launch: the next forward's neck may rewrite the attention maps after it
-        cur_stream = 0;
+        reached(kPtDecodersEnd);
     }
     const int* widths() const {
         static const int w0[4] = {32, 48, 96, 176}, w1[4] = {32, 48, 120, 224}, w2[4] = {32, 64, 144, 288};
@@ -1764,7 +1740,6 @@ public:
         if (!direct0) {
             ToNhwcParams tp{nullptr, x.p, B, 3, R, R, x.ld};
             const void** rin = &io.radar;
-            mark_xwait_next(kXFusion);   // pipelined forwards: this branch rewrites the radar pyramid the previous forward's fusion reads
             const double bytes = double(x.rows()) * (3 + 3) * sizeof(T), lbytes = double(x.rows()) * (3 + x.ld) * sizeof(T);
             const bool alt = io_alt();
             if (narrow0) {
@@ -1805,7 +1780,6 @@ public:
                 const dim3 grid(unsigned(cdivl(long(B) * (x.H / POOLN_ROWS) * (x.W / 4), 256))), block(256);
                 const void** rin = &io.radar;
                 const bool alt = io_alt();
-                mark_xwait_next(kXFusion);   // pipelined forwards: this branch rewrites the radar pyramid the previous forward's fusion reads
                 add_op(pfx + ".avgpool", [pp, grid, block, rin, alt](hipStream_t s) mutable { pp.X = *rin; if (alt) ACH_LAUNCH((avgpool3x3_nchw3_kernel<T, IOB>), grid, block, s, pp); else ACH_LAUNCH((avgpool3x3_nchw3_kernel<T, T>), grid, block, s, pp); },
                        2.0 * x.rows() * C * sizeof(T), 0, double(x.rows()) * (3 + pooled.ld) * sizeof(T));
                 }
@@ -1965,7 +1939,7 @@ public:
         {
             const dim3 grid(unsigned(cdivl(fuse_max, 256)), unsigned(n)), block(256);
             add_op(e + ".fusion.apply", [mf, grid, block](hipStream_t s) { ACH_LAUNCH(fuse_scale_multi_kernel<T>, grid, block, s, mf); }, bytes);
-            mark_xsignal_last(kXFusion); // last reader of the FPN outputs / radar pyramid (and, in stream order, after the decoders' reads)
+            reached(kPtFusion);
         }
     }
 
@@ -2309,24 +2283,14 @@ public:
         // enqueue order = plan order: the two side branches first, so they are already running while the (longest) image
         // path is being enqueued on the caller's stream
         A r[3];
-        // "head_stream": PointNet queues behind the radar branch on the low-priority stream; the (four times longer) PointNet++
-        // branch opens stream 2 instead, ahead of fusion + head, which only start once the neck is done (measured +4.8 %; PointNet: neutral)
-        // (auto: stream 2 for PointNet++, and in the pipelined plan, where it shares the stream with the decoders: 27.7 k against 26.4 k
-        //  frames/s; the plain plan keeps PointNet on stream 1 ahead of the radar branch — two streams in all: 26.35 k against 25.95 k)
-        const bool point2 = point_on_head_stream < 0 ? (cfg.pc_seg == ACH_PCSEG_PN2 || cfg.pc_seg == ACH_PCSEG_PN2_MSG || (!head_stream && pipeline)) : point_on_head_stream != 0;
-        const bool radar_late = radar_start_eff() >= 0 && multi_stream;
-        auto points = [&] { cur_stream = point_on_head_stream == 3 ? 3 : (point2 ? 2 : 1); if (cfg.pc_seg == ACH_PCSEG_PN2 || cfg.pc_seg == ACH_PCSEG_PN2_MSG) pointnet2(); else if (cfg.pc_seg == ACH_PCSEG_PN) pointnet(); };   // ACH_PCSEG_NONE: Achelous3T
-        if (radar_late) points();         // the point branch (small launches) fills the window before the radar branch is released
-        cur_stream = 1;
-        if (radar_late) wait_before_next(0);
-        rcnet(r);
-        signal_after_last(3);             // radar pyramid ready
-        if (!radar_late) points();
-        cur_stream = 0;
+        sched = make_schedule(*this);     // streams, joins and cross-forward marks: engine_schedule.h
+        auto points = [&] { enter(kSegPoints); if (cfg.pc_seg == ACH_PCSEG_PN2 || cfg.pc_seg == ACH_PCSEG_PN2_MSG) pointnet2(); else if (cfg.pc_seg == ACH_PCSEG_PN) pointnet(); };   // ACH_PCSEG_NONE: Achelous3T
+        if (sched.points_first) points();
+        enter(kSegRadar); rcnet(r); reached(kPtRadarPyramid);
+        if (!sched.points_first) points();
+        enter(kSegBackbone);
         A m[4];
         cat_buf[0] = A(); cat_buf[1] = A();
-        // the neck on stream 2 needs the stage outputs' launches to be identifiable (the preset concat slices of the EdgeNeXt plans) and the radar branch released before stage 3
-        neck_on_side = pipeline && multi_stream && split_decoders == 0 && dec_fork == 3 && cfg.backbone == ACH_BACKBONE_EDGENEXT && radar_start_eff() < 3;
         if (cfg.backbone == ACH_BACKBONE_EDGENEXT) {
             // stage 1 / stage 2 outputs go straight into the second half of the neck's concat buffers (no cat copy)
             const int* wd = widths();
@@ -2341,17 +2305,10 @@ public:
         A q[3];
         neck(m, q);
         tap("q3", q[0]); tap("q4", q[1]); tap("q5", q[2]);
-        // detection branch: fusion + head continue on the RADAR stream (in order after the radar taps), gated only on the FPN
-        // outputs (event 1) — they overlap with the segmentation decoders that keep the caller's stream busy
-        // ("head_stream": on stream 2 at the caller's priority, gated on both the FPN outputs and the radar pyramid)
-        cur_stream = head_stream ? 2 : 1;
-        detect_stream = cur_stream;
-        wait_before_next(1);
-        if (head_stream) wait_before_next2(3);
+        enter(kSegDetect);
         A p[3];
         fuse_all(q, r, p);
         head(p);
-        cur_stream = 0;
         interleave_streams();
     }
 
@@ -2366,21 +2323,20 @@ public:
         const size_t total = ops.size();
         ops.clear();
         std::vector<size_t> pos(seq.size(), 0);
-        bool signalled[kJoinEvents] = {false, false, false, false};
+        unsigned signalled = 0;
         while (ops.size() < total) {
             // pick the stream that is furthest behind its proportional share and whose next launch is not blocked
             int best = -1; double best_lag = -1e30;
             for (size_t k = 0; k < seq.size(); ++k) {
                 if (pos[k] >= seq[k].size()) continue;
                 const Op& nx = seq[k][pos[k]];
-                if (nx.wait_ev >= 0 && !signalled[nx.wait_ev]) continue;
-                if (nx.wait_ev2 >= 0 && !signalled[nx.wait_ev2]) continue;
+                if (nx.wait & ~signalled) continue;
                 const double lag = double(ops.size() + 1) * double(seq[k].size()) / double(total) - double(pos[k]);
                 if (lag > best_lag) { best_lag = lag; best = int(k); }
             }
             if (best < 0) throw AchError{ACH_ERR_INVALID, "plan interleave: unsatisfiable event order"};
             Op& op = seq[size_t(best)][pos[size_t(best)]++];
-            if (op.signal_ev >= 0) signalled[op.signal_ev] = true;
+            signalled |= op.signal;
             ops.push_back(std::move(op));
         }
     }
@@ -2404,9 +2360,9 @@ public:
         if (aneed > aarena_cap) { if (aarena) (void)hipFree(aarena); aarena = nullptr; aarena_cap = 0; ACH_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&aarena), aneed)); aarena_cap = aneed; }
         // The measuring pass consumes no mark (add_op returns early), so every cross-forward wait it marked is still pending and lands on the FIRST launch of the plan: not
         // designed, but the schedule every measurement and pipelined bit-identity run so far was made with; kept until a change of its own removes it with an A/B.
-        const unsigned char first_launch_xwait = pending_xwait;
+        const unsigned char first_launch_xwait = pending.xwait;
         reset_plan(B);
-        pending_xwait = first_launch_xwait;
+        pending.xwait = first_launch_xwait;
         post_plan.clear();
         build();
         ACH_HIP_CHECK(hipMemset(aarena, 0, aarena_used));      // channel padding lanes stay zero for the lifetime of the plan

@@ -222,6 +222,18 @@ class NativeEngine:
                      layout_bytes=self.L.ach_op_layout_bytes(self.h, i), flops=self.L.ach_op_flops(self.h, i),
                      stream=self.L.ach_op_stream(self.h, i)) for i in range(self.launches())]
 
+    def op_schedule(self):
+        """[{op, stream, wait, signal, xwait, xsignal}] of every launch in the plan: the stream it runs on and the events it waits for / records,
+        as the bit masks of ach_op_sync (include/achelous.h)."""
+        out = []
+        for i in range(self.launches()):
+            m = [ctypes.c_int() for _ in range(4)]
+            if self.L.ach_op_sync(self.h, i, *map(ctypes.byref, m)) != 0:
+                raise IndexError(f'launch {i} is outside the plan')
+            out.append(dict(op=self.L.ach_op_name(self.h, i).decode(), stream=self.L.ach_op_stream(self.h, i),
+                            wait=m[0].value, signal=m[1].value, xwait=m[2].value, xsignal=m[3].value))
+        return out
+
     def forward_profiled(self, image, radar, points, outs, stream=0):
         """One forward with every launch bracketed by HIP events -> per-launch milliseconds."""
         n = self.launches()

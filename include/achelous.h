@@ -312,6 +312,11 @@ double ach_op_bytes(const ach_handle* h, int i);          /* inputs read once + 
 double ach_op_layout_bytes(const ach_handle* h, int i);   /* the same over the stored pixel pitches (channel padding included) */
 double ach_op_flops(const ach_handle* h, int i);          /* 2 x MACs of the dense contractions of the launch */
 int ach_op_stream(const ach_handle* h, int i);            /* 0: caller's stream, 1..: engine side streams */
+/* read-only look at the plan's schedule: the events launch `i` waits for before it starts and records once it is enqueued, as bit masks.  `wait` / `signal`: the
+ * joins inside one forward (bit 0 radar release, 1 FPN outputs, 2 decoder fork, 3 radar pyramid); `xwait` / `xsignal`: the cross-forward marks of the pipelined plan
+ * (bit 0 fusion's reads, 1 the decoders' reads, 2 the neck's reads; placed in every plan, honoured only under option "pipeline").  A launch outside the plan:
+ * ACH_ERR_INVALID.  tests/golden/plan_schedules.json pins these for a set of plans. */
+int ach_op_sync(const ach_handle* h, int i, int* wait, int* signal, int* xwait, int* xsignal);
 int ach_forward_profiled(ach_handle* h, const void* image, const void* radar, const void* points,
                          void* det3, void* det4, void* det5, void* se_seg, void* lane_seg, void* pc_seg, void* stream,
                          float* op_ms, size_t capacity);

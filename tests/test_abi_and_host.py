@@ -70,7 +70,7 @@ def test_bindings_derived_from_the_header_have_the_declared_signatures():
     for name, (restype, argtypes) in literal.items():
         assert eng_mod.PROTOTYPES[name] == (restype, argtypes), name
     counts = _declared_parameter_counts()
-    assert list(eng_mod.NativeLibrary.SYMBOLS) == list(eng_mod.PROTOTYPES) and set(counts) == set(eng_mod.PROTOTYPES) and len(counts) == 89
+    assert list(eng_mod.NativeLibrary.SYMBOLS) == list(eng_mod.PROTOTYPES) and set(counts) == set(eng_mod.PROTOTYPES) and len(counts) == 90
     L = emu_library().lib
     for name, n in counts.items():
         fn = getattr(L, name)
@@ -316,3 +316,19 @@ def test_the_shipped_kernels_contain_no_16x16x32_matrix_instruction():
         text = open(os.path.join(csrc, 'build', tu)).read()
         assert text.count('v_mfma_f32_16x16x16') > 100, tu
         assert 'v_mfma_f32_16x16x32' not in text, tu
+
+
+def test_plan_schedules_equal_the_committed_listing():
+    """Streams, joins and cross-forward marks of every plan of tests/plan_schedules.py, rebuilt on the CPU emulation library, against tests/golden/plan_schedules.json
+    (generated from the commit before the schedule was stated once, csrc/engine_schedule.h).  The emulation's event calls are no-ops and a wrong schedule is a rare
+    race on the GPU: this listing is what notices a launch that changed its stream or lost a wait.  A deliberate change of schedule regenerates the file."""
+    import plan_schedules as PS
+    from emu_util import emu_library
+    with open(PS.SCHEDULES_JSON) as f:
+        want = json.load(f)['plans']
+    got = {pid: PS.summary(full) for pid, full in PS.all_plans(emu_library())}
+    assert list(got) == list(want)
+    assert [pid for pid in want if got[pid] != want[pid]] == []
+    assert sum('error' in p for p in want.values()) == 6 and all('unsatisfiable event order' in p['error'] for p in want.values() if 'error' in p)
+    lib = emu_library().lib
+    assert lib.ach_op_sync(None, 0, None, None, None, None) == -1       # no handle, no launch: ACH_ERR_INVALID

@@ -1307,3 +1307,58 @@ def test_stale_plans_are_refused(dtype):
     piped.set_option('dec_fork', 2)
     piped.join(torch.cuda.current_stream().cuda_stream)
     assert piped.forwards_in_flight() == 0 and same(o, want_b)
+
+
+_SCHEDULE_CASE = {}
+
+
+def _schedule_case():
+    """en_s0 at 160 x 160, batch 8, 64 points, bf16 tensors on fp16 storage: three inputs, and the outputs of three consecutive forwards on a `streams = 0` engine
+    (computed once, shared by every case of the test below and left unchanged)"""
+    if not _SCHEDULE_CASE:
+        from emu_util import alloc_outputs
+        g = Golden('en_s0')
+        kw = dict(ctor_kwargs(g.meta), resolution=160)
+        sd = g.calibrate(condition_state_dict(Achelous(**kw).state_dict(), seed=g.meta['weight_seed']))
+        ins = [tuple(t.cuda().to(torch.bfloat16) for t in make_inputs(8, 1300 + i, resolution=160, num_points=64, pc_channels=kw['pc_channels'], dense_radar=(i == 1)))
+               for i in range(3)]
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def run(**options):
+            e = eng_mod.NativeEngine(eng_mod.hip_library(), num_det=kw['num_det'], num_seg=kw['num_seg'], phi=kw['phi'], backbone=kw['backbone'], resolution=160,
+                                     pc_channels=kw['pc_channels'], pc_classes=kw['pc_classes'], num_points=64, nano_head=kw['nano_head'], spp=kw['spp'],
+                                     dtype=eng_mod.DTYPE_F16, neck=kw['neck'], pc_seg=kw['pc_seg'])
+            e.set_option('io_bf16', 1)
+            for k, v in options.items():
+                e.set_option(k, v)
+            e.load_state_dict(sd)
+            e.plan(8)
+            outs = [alloc_outputs(kw, 8, 64, torch.bfloat16, 'cuda') for _ in ins]
+            for (x, xr, xp), o in zip(ins, outs):
+                e.forward(x, xr, xp, o, stream)
+            while e.forwards_in_flight():
+                e.join(stream)
+            torch.cuda.synchronize()
+            e.destroy()
+            return outs
+        _SCHEDULE_CASE.update(run=run, want=run(streams=0))
+    return _SCHEDULE_CASE['run'], _SCHEDULE_CASE['want']
+
+
+def _schedule_option_sets():
+    import plan_schedules as PS
+    return [pytest.param(o, id=PS.option_id(o)) for o in PS.OPTION_SETS if o != {'radar_start': 4}]       # (EdgeNeXt with radar_start = 4 does not plan)
+
+
+@pytest.mark.parametrize('options', _schedule_option_sets())
+def test_every_schedule_form_is_bit_identical_to_one_stream(options):
+    """The option sets that change the schedule (csrc/engine_schedule.h; the same sets as tests/golden/plan_schedules.json): three consecutive forwards on three
+    different inputs, the pipelined forms joined at the end, equal bit for bit the same three forwards of a `streams = 0` engine.  A plumbing check of run_eager's
+    wait / record loops against real events — launches this short rarely overlap across streams; that the schedule itself is the intended one is what the
+    committed listing pins."""
+    run, want = _schedule_case()
+    got = run(**options)
+    for k, (a, b) in enumerate(zip(got, want)):
+        for u, v in zip(a, b):
+            assert torch.equal(u, v), (options, k)
+    assert any(float(t.float().abs().max()) > 0 for t in want[0])
