@@ -1,5 +1,5 @@
 // api_frames.cpp — the entries that work on ragged batches of frames: the resample pass, training batches and radar inputs assembled on the device (k_data.h,
-// k_radarmap.h), serving at every frame's own size (k_serve.h) and drawing (k_draw.h).  What they share is the host-side check of a frame table against its arenas
+// k_radarmap.h), serving at every frame's own size (k_serve.h), drawing (k_draw.h) and the heat-map mode (k_heatmap.h).  What they share is the host-side check of a frame table against its arenas
 // BEFORE anything is launched: a bad table must never become an out-of-bounds access on the device.  See api.cpp / api_util.h.
 #include <algorithm>
 #include <cmath>
@@ -11,6 +11,8 @@
 #include "k_radarmap.h"
 #include "k_serve.h"
 #include "k_draw.h"
+#include "k_heatmap.h"
+#include "../../include/achelous_heatmap.h"
 
 static const int64_t SIZE_TOP = (1L << 30) - 1;      // a frame's H and W (the drawing entry has a limit of its own)
 static_assert(int(ach::DATA_F32) == KIND_F32 && int(ach::DATA_BF16) == KIND_BF16 && int(ach::DATA_F16) == KIND_F16 && int(ach::DATA_U8_HWC) == KIND_U8, "the data entries' kinds are ElemKind");
@@ -257,6 +259,49 @@ int ach_draw_detections_frames(uint8_t* arena, int64_t arena_bytes, const int64_
         ach::DrawParams p{boxes, count, records, arena, reinterpret_cast<const long long*>(table_dev), labels_dev, blob_dev, style_dev, class_counts, max_det, num_classes};
         ACH_LAUNCH(ach::draw_prepare_kernel, dim3(unsigned(batch)), dim3(256), s, p);
         ACH_LAUNCH(ach::draw_tiles_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
+    });
+}
+
+// ---- the heat-map mode on served frames (k_heatmap.h): cell scores, the uint8 mask at every frame's own size with its range, and the colour-mapped blend over a base
+// arena, in three launches (two without colour).  Stateless.  The host copy of the frame table is checked against every arena before anything is launched.
+int ach_heatmap_frames(int32_t det_kind, int32_t R, int32_t num_det, int32_t batch, const void* det3, const void* det4, const void* det5, float* scores,
+                       const uint8_t* base, int64_t base_bytes, const int64_t* table_host, const int64_t* table_dev, const uint8_t* cmap_dev, float alpha,
+                       uint8_t* mask, int64_t mask_bytes, int32_t* stats, uint8_t* out, int64_t out_bytes, void* stream) {
+    return stateless(stream, [&](hipStream_t s) {
+        need(det3 && det4 && det5 && scores && table_host && table_dev && mask && stats && batch > 0 && batch <= 65535 && mask_bytes >= 0, "ach_heatmap_frames");
+        need(det_kind >= KIND_F32 && det_kind <= KIND_F16, "ach_heatmap_frames: det_kind is 0 (fp32), 1 (bf16) or 2 (fp16)");
+        need(R >= 32 && R <= 16384 && R % 32 == 0, "ach_heatmap_frames: R is a multiple of 32");
+        need(num_det >= 1 && num_det <= 4096, "ach_heatmap_frames: num_det is 1..4096");
+        const int A = ach::heat_cells(R);
+        if (A > ach::HEAT_MAX_CELLS) throw ach::AchError{ACH_ERR_UNSUPPORTED, "ach_heatmap_frames: more than 4096 cells per frame (R above 416)"};
+        need(aligned16(mask, out) && (reinterpret_cast<uintptr_t>(scores) & 3u) == 0 && (reinterpret_cast<uintptr_t>(stats) & 3u) == 0, "ach_heatmap_frames: the mask and out arenas are 16-byte aligned");
+        const bool colour = out != nullptr;
+        if (colour) {
+            need(base && cmap_dev && base_bytes > 0 && base_bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(base) & 3u) == 0 && out_bytes >= 0,
+                 "ach_heatmap_frames: colour needs the base arena (4-byte aligned, padded to 4 bytes), the colour map and the out arena");
+            need(alpha >= 0.f && alpha <= 1.f, "ach_heatmap_frames: alpha lies in [0, 1]");
+        }
+        long blocks = 0;
+        for (int b = 0; b < batch; ++b) {
+            const int64_t* f = table_host + long(b) * ach::HEAT_TABLE_COLS;
+            const int64_t H = f[1], W = f[2], y0 = f[4], x0 = f[5], nh = f[6], nw = f[7];
+            need(dims_ok(H, W, SIZE_TOP), "ach_heatmap_frames: a frame's H and W are at least 1");
+            need(nh >= 1 && nw >= 1 && y0 >= 0 && x0 >= 0 && nh <= R - y0 && nw <= R - x0, "ach_heatmap_frames: a frame's window leaves the network input");
+            need(frame_fits(f[8], H, W, f[9], f[9], mask_bytes, 16), "ach_heatmap_frames: a frame's mask passes its arena (offset and pitch are multiples of 16, pitch >= W)");
+            if (colour) {
+                need(frame_fits(f[0], H, 3 * W, f[3], 3 * W, base_bytes), "ach_heatmap_frames: a frame's extent passes the base arena");
+                need(frame_fits(f[10], H, 3 * W, f[11], f[11], out_bytes, 16), "ach_heatmap_frames: a coloured frame passes the out arena (offset and pitch are multiples of 16, pitch >= 3 W)");
+                // in place: the frame is written where it is read, so it lies in `out` exactly as in `base`
+                if (out == base) need(f[10] == f[0] && f[11] == f[3], "ach_heatmap_frames: in place, a frame's out offset and pitch are its base offset and pitch");
+            }
+            blocks = std::max(blocks, ach::cdivl(W, ach::HEAT_TW) * ach::cdivl(H, ach::HEAT_TH));
+        }
+        need(blocks < (1L << 31), "ach_heatmap_frames: a frame is too large");
+        ach::HeatScoreParams sp{{det3, det4, det5}, scores, stats, R, num_det, A};
+        by_kind(det_kind, [&](auto e) { ACH_LAUNCH(ach::heat_scores_kernel<typename decltype(e)::type>, dim3(unsigned(ach::cdivl(A, 256)), unsigned(batch)), dim3(256), s, sp); });
+        ach::HeatParams p{scores, stats, base, reinterpret_cast<const long long*>(table_dev), cmap_dev, mask, out, R, A, alpha};
+        ACH_LAUNCH(ach::heat_mask_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
+        if (colour) ACH_LAUNCH(ach::heat_colour_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
     });
 }
 

@@ -67,9 +67,17 @@ def parse_header(text):
 with open(HEADER) as _f:
     PROTOTYPES = parse_header(_f.read())
 
+# extension headers next to include/achelous.h: entries declared outside it, read and bound the same way (include/achelous_heatmap.h: the heat-map mode)
+EXTENSION_HEADERS = ('achelous_heatmap.h',)
+EXTENSIONS = {}
+for _name in EXTENSION_HEADERS:
+    with open(os.path.join(os.path.dirname(HEADER), _name)) as _f:
+        EXTENSIONS.update(parse_header(_f.read()))
+
 
 class NativeLibrary:
-    """dlopen + prototypes for every symbol declared in include/achelous.h, derived from the header itself (parse_header)."""
+    """dlopen + prototypes for every symbol declared in include/achelous.h (SYMBOLS) and in its extension headers (EXTENSIONS), derived from the headers themselves
+    (parse_header)."""
     SYMBOLS = tuple(PROTOTYPES)
 
     def __init__(self, path):
@@ -80,7 +88,7 @@ class NativeLibrary:
         self.lib = ctypes.CDLL(path)
         # (an entry is bound where the library exports it: the co-residency tests also load libraries built from older sources; tests/test_abi_and_host.py
         #  holds the product to every declared symbol, and calling an entry a library lacks raises AttributeError)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **EXTENSIONS}.items():
             fn = getattr(self.lib, name, None)
             if fn is not None:
                 fn.restype, fn.argtypes = restype, argtypes
@@ -312,6 +320,18 @@ class NativeEngine:
         """`correct_boxes` with a (H, W) per frame: int32 [batch, 2], host copy and device copy (raw addresses)"""
         self._check(self.L.ach_correct_boxes_frames(self.h, int(batch), int(max_det), _ptr(rows), _ptr(count), ctypes.c_void_p(shapes_host), ctypes.c_void_p(shapes_dev),
                                                     int(bool(letterbox)), _ptr(out), ctypes.c_void_p(stream)))
+
+    @staticmethod
+    def heatmap_frames(lib, det_kind, resolution, num_det, batch, det3, det4, det5, scores, base, base_bytes, table_host, table_dev, cmap_dev, alpha, mask, mask_bytes,
+                       stats, out, out_bytes, stream=0):
+        """the heat-map mode of a ragged batch in three launches (include/achelous_heatmap.h ach_heatmap_frames): stateless, so `lib` (a `NativeLibrary`) stands where the
+        handle would; the table / colour map arguments are raw addresses, every other pointer a tensor or None (base, out: no colour pass)"""
+        vp = ctypes.c_void_p
+        rc = lib.lib.ach_heatmap_frames(int(det_kind), int(resolution), int(num_det), int(batch), _ptr(det3), _ptr(det4), _ptr(det5), _ptr(scores), _ptr(base),
+                                        int(base_bytes), vp(table_host), vp(table_dev), vp(cmap_dev), float(alpha), _ptr(mask), int(mask_bytes), _ptr(stats), _ptr(out),
+                                        int(out_bytes), vp(stream))
+        if rc != 0:
+            raise _ERRORS.get(rc, RuntimeError)((lib.lib.ach_last_error(None) or b'ach_heatmap_frames failed').decode())
 
     # ---------------------------------------------------------------------------------------------------
     def tap_names(self):

@@ -10,6 +10,7 @@
     detect_frames(net, frames, radar, points)        achelous.py:190-345    camera bytes of B frames of different sizes -> boxes, class maps, overlays
     detect_frames_from_clouds(net, frames, clouds)   + radar_feature_map_generate.ipynb   the same from raw radar point clouds (data.radar_maps_batch / radar_points_batch)
     draw_detections_frames(arena, layout, boxes, ..) achelous.py:363-433    box rings, label plates and label text drawn in place on every frame, PIL's bytes (csrc/k_draw.h)
+    heatmap_frames(det, shapes, base, layout, style) achelous.py:451-555    the heat-map mode: score mask at every frame's size, its range, the jet blend (csrc/k_heatmap.h)
 HIP kernels through the C ABI; no CPU fallback.
 """
 import contextlib
@@ -18,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from ._native import lib as _pass_lib, check as _check, ptr as _ptr, stream as _stream, stateless_handle
+from ._native import lib as _pass_lib, check as _check, ptr as _ptr, stream as _stream, stateless_handle, DTYPE_CODE as _DTYPE_CODE
 from .postprocess import _handle
 
 # `_pass_lib(t)` is `_native.lib` (tests set `_pass_lib.test_library`): it raises RuntimeError for a CPU tensor.  The single-shape entries below always run on the
@@ -496,7 +497,7 @@ def draw_detections_frames(arena, layout, boxes, count, shapes, style, input_sha
     them, `shapes` one (H, W) per frame, `style` a `DrawStyle`, `input_shape` the network's (R, R).  class_counts: optional int32 [B, num_classes] tensor that receives
     the number of kept rows per class id (the reference's count=True tally; skipped classes count, rows past count[b] do not).
     Two launches whatever B is; the per-frame table travels in one non-blocking copy; no host read, no synchronisation.  Returns the per-frame [H, W, 3] views.
-    Not covered: crop=True (data-dependent output sizes), the matplotlib scatter of the point classes, the heat-map mode, file output."""
+    Not covered: crop=True (data-dependent output sizes), the matplotlib scatter of the point classes, file output."""
     from . import data as _data
     lib = _pass_lib(arena)
     if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
@@ -531,8 +532,124 @@ def draw_detections_frames(arena, layout, boxes, count, shapes, style, input_sha
     return [torch.as_strided(arena, (h, w, 3), (int(pitches[b]), 3, 1), int(offs[b])) for b, (h, w) in enumerate(shapes)]
 
 
+# ------------------------------------------------------------------------------------------------- the heat-map mode (csrc/k_heatmap.h)
+HEAT_TABLE_COLS = 16        # k_heatmap.h
+
+
+class HeatmapStyle:
+    """How `heatmap_frames` colours: `alpha` of the colour over the base image (the reference's 0.5), `cmap` uint8 [256, 3] (None: matplotlib's jet, shipped as a table:
+    `colormaps.JET`), `window`: 'full' stretches every level's whole map over the frame as the reference does, 'letterbox' only the part the frame's letterbox fills,
+    `over` (read by `detect_frames`): 'frame' colours the camera frame as the reference does, 'overlay' the segmentation overlay."""
+
+    def __init__(self, alpha=0.5, cmap=None, window='full', over='frame'):
+        from .colormaps import JET
+        self.alpha = float(alpha)
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError("HeatmapStyle: alpha lies in [0, 1]")
+        c = JET if cmap is None else np.asarray(cmap)
+        if c.dtype != np.uint8 or c.shape != (256, 3):
+            raise ValueError("HeatmapStyle: `cmap` is a uint8 [256, 3] table")
+        if window not in ('full', 'letterbox') or over not in ('frame', 'overlay'):
+            raise ValueError("HeatmapStyle: window is 'full' or 'letterbox', over is 'frame' or 'overlay'")
+        self.cmap, self.window, self.over = np.ascontiguousarray(c), window, over
+
+
+def heatmap_frames(det, shapes, base, layout=None, style=None, input_shape=None, letterbox_image=True, out=None, inplace=False):
+    """The reference's heat-map mode (achelous.detect_heatmap, achelous.py:451-555) for B frames of different sizes, from the detection maps `det` = (det3, det4, det5)
+    [B, 5 + num_det, R/s, R/s] (s = 8, 16, 32; fp32, bf16 or fp16) that `forward_detect` returns, in three launches whatever B is:
+
+    heat_mask: per frame the uint8 [H, W] mask max_l uint8(trunc(cv2.resize(max_c sigmoid(cls) * sigmoid(obj), (W, H)) * 255)) — the reference's arithmetic
+    (achelous.py:457-459, 539-546; INTER_LINEAR as `oracle/prepost.py:resize_linear` restates it, float32, never contracted).  A cell with a NaN logit scores 0.
+    heat_range: int32 [B, 2] = (lo, hi), the mask's minimum and maximum, which is what matplotlib's Normalize scales the colour map by.
+    heatmap: per frame uint8 [H, W, 3] = Image.blend(base, cmap[min(int((m - lo) / (hi - lo) * 256), 255)], alpha), entry 0 on a flat mask: the colour is byte for byte
+    `matplotlib.cm.jet(Normalize(lo, hi)(mask), bytes=True)`, the compositing is PIL's `Image.blend`, at the frame's own size.  matplotlib's Agg compositing and its
+    resampling to the figure's size (achelous.py:548-553) are NOT reproduced.
+
+    style.window: 'full' is the reference, which stretches the whole map over the frame even when the frame was letterboxed; 'letterbox' (with letterbox_image=True)
+    stretches the window `letterbox_window` gives instead, so that the heat lies on what it belongs to.  The interpolation still clamps at the map's edge, not the
+    window's, so up to half a cell of the grey bars' score bleeds in at the window's edge.
+
+    base: the image under the colour — a `data.Arena` (layout: None) or a 1-D uint8 tensor of packed HWC frames with `layout` = (byte offsets, pitches) per frame or
+    what `frames_layout(shapes)` returns (its overlay part); None: mask and range only (two launches).  The coloured frames go to an arena of their own laid out by
+    `frames_layout` (`out`: a 1-D uint8 tensor to use), or with inplace=True over `base` itself (its offsets and pitches are then multiples of 16, as an overlay
+    arena's are).  input_shape: the network's (R, R), default 8 x det3's size.  Returns dict(heat_mask, heat_range, heatmap (with a base), scores float32 [B, A]
+    level-major, arenas).  One non-blocking copy for the tables; no host read, no synchronisation."""
+    from . import data as _data
+    from .engine import NativeEngine
+    style = HeatmapStyle() if style is None else style
+    if len(det) != 3 or any(d.dim() != 4 or d.dtype != det[0].dtype or d.device != det[0].device or d.shape[:2] != det[0].shape[:2] for d in det):
+        raise ValueError("heatmap_frames: det = (det3, det4, det5), [B, 5 + num_det, R/s, R/s] of one dtype on one device")
+    det = [d.contiguous() for d in det]
+    lib = _pass_lib(det[0])
+    if det[0].dtype not in _DTYPE_CODE:
+        raise TypeError(f"heatmap_frames: float32, bfloat16 or float16 detection maps, got {det[0].dtype}")
+    B, C = int(det[0].shape[0]), int(det[0].shape[1])
+    R = 8 * int(det[0].shape[2]) if input_shape is None else int(input_shape[0])
+    if C < 6 or (input_shape is not None and int(input_shape[1]) != R) or any(tuple(d.shape[2:]) != (R // s, R // s) for d, s in zip(det, (8, 16, 32))):
+        raise ValueError("heatmap_frames: det maps of [B, 5 + num_det, R/8 | R/16 | R/32 squared] for a square input_shape (R, R) expected")
+    shapes = _frame_shapes(shapes, B)
+    dev = det[0].device
+    A = (R // 8) ** 2 + (R // 16) ** 2 + (R // 32) ** 2
+    moff, mp, mbytes, ooff, op, obytes = frames_layout(shapes)
+    table = np.zeros((B, HEAT_TABLE_COLS), np.int64)
+    for b, (h, w) in enumerate(shapes):
+        table[b, 1:3] = (h, w)
+        table[b, 4:8] = letterbox_window(h, w, R) if (style.window == 'letterbox' and letterbox_image) else (0, 0, R, R)
+        table[b, 8:12] = (moff[b], mp[b], ooff[b], op[b])
+    base_t = None
+    if base is not None:
+        if isinstance(base, _data.Arena):
+            if len(base.frames) != B or any(f is None or (f[1], f[2]) != sh for f, sh in zip(base.frames, shapes)):
+                raise ValueError("heatmap_frames: `base` holds one image per frame, of the sizes in `shapes`")
+            base_t, boffs, bpitches = base.data, [f[0] for f in base.frames], [f[3] for f in base.frames]
+        else:
+            if layout is None:
+                raise ValueError("heatmap_frames: a tensor `base` needs its `layout`")
+            base_t = base
+            boffs, bpitches = (layout[3], layout[4]) if len(layout) == 6 else layout
+        if base_t.dtype != torch.uint8 or base_t.dim() != 1 or not base_t.is_contiguous() or base_t.device != dev:
+            raise ValueError("heatmap_frames: `base` is a contiguous 1-D uint8 tensor on the det maps' device")
+        if len(boffs) != B or len(bpitches) != B:
+            raise ValueError("heatmap_frames: one offset and one pitch per frame")
+        for b in range(B):
+            table[b, 0], table[b, 3] = int(boffs[b]), int(bpitches[b])
+        if inplace:
+            table[:, 10], table[:, 11] = table[:, 0], table[:, 3]
+    elif inplace or out is not None:
+        raise ValueError("heatmap_frames: `out` / inplace need a `base`")
+    meta = _data._Meta(dev, 'serve_heat')
+    tref, cref = meta.add(table), meta.add(style.cmap)
+    meta.commit()
+    scores = torch.empty(B, A, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    mask = torch.empty(max(mbytes, 16), dtype=torch.uint8, device=dev)
+    out_t = None
+    if base_t is not None:
+        if inplace:
+            if out is not None:
+                raise ValueError("heatmap_frames: inplace=True writes over `base`; no `out`")
+            out_t = base_t
+        elif out is None:
+            out_t = torch.empty(max(obytes, 16), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < obytes:
+            raise ValueError(f"heatmap_frames: `out` is a contiguous 1-D uint8 tensor of at least {obytes} bytes on the det maps' device")
+        else:
+            out_t = out
+    ctx = torch.cuda.device(dev) if det[0].is_cuda else contextlib.nullcontext()
+    with ctx:
+        NativeEngine.heatmap_frames(lib, _DTYPE_CODE[det[0].dtype], R, C - 5, B, det[0], det[1], det[2], scores, base_t, 0 if base_t is None else base_t.numel(),
+                                    meta.host_ptr(tref).value, meta.dev_ptr(tref).value, meta.dev_ptr(cref).value, style.alpha, mask, mask.numel(), stats, out_t,
+                                    0 if out_t is None else out_t.numel(), _stream(det[0]).value)
+    res = {'heat_mask': [torch.as_strided(mask, (h, w), (mp[b], 1), moff[b]) for b, (h, w) in enumerate(shapes)],
+           'heat_range': torch.stack((255 - stats[:, 1], stats[:, 0]), dim=1), 'scores': scores, 'arenas': {'heat_mask': mask}}
+    if out_t is not None:
+        res['heatmap'] = [torch.as_strided(out_t, (h, w, 3), (int(table[b, 11]), 3, 1), int(table[b, 10])) for b, (h, w) in enumerate(shapes)]
+        res['arenas']['heatmap'] = out_t
+    return res
+
+
 def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4, letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True,
-                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3, draw=None):
+                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3, draw=None, heatmap=None):
     """`detect_frame` for B frames of DIFFERENT sizes: the arithmetic of the reference's detect_image (achelous.py:190-433) without its file I/O; the box drawing
     (achelous.py:363-433) is on with `draw`.
 
@@ -545,24 +662,29 @@ def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4
     Returns dict(boxes [B, max_det, 7] = (y1, x1, y2, x2 in the frame's own pixels, obj, class conf, class id), rows past count[b] zero; count [B] int32;
     semantic, waterline: lists of [H_i, W_i] uint8 views; overlay: list of [H_i, W_i, 3] uint8 views (overlay=True; `seg_maps_frames`); point_class [B, N] int64).
     draw: None, or a `DrawStyle` — two more launches (`draw_detections_frames`) then draw every kept detection's box, plate and label on the overlay (overlay=True
-    is required), and the result gains class_counts [B, num_classes] int32, the kept rows per class id.  With draw=None nothing changes."""
+    is required), and the result gains class_counts [B, num_classes] int32, the kept rows per class id.  With draw=None nothing changes.
+    heatmap: None, or a `HeatmapStyle` — three more launches (`heatmap_frames`) on the det maps of the same `forward_detect`, and the result gains heat_mask,
+    heat_range and heatmap; the colour goes over the camera frames (style.over = 'frame', the reference) or over the overlay as it is after the drawing ('overlay',
+    needs overlay=True), into an arena of its own: every other key is what it is without `heatmap`, and with heatmap=None nothing changes."""
     from . import data as _data
-    _need_overlay(draw, overlay)
+    _need_overlay(draw, overlay, heatmap)
     R = net.resolution
     arena = _data._as_arena(frames, 3, radar_maps.device, 'images')
     B = len(arena.frames)
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = preprocess_input_radar(radar_maps, dtype)
     xp = normalize_points(points, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap)
 
 
-def _need_overlay(draw, overlay):
+def _need_overlay(draw, overlay, heatmap=None):
     if draw is not None and not overlay:
         raise ValueError("detect_frames: `draw` draws on the overlay, so it needs overlay=True")
+    if heatmap is not None and heatmap.over == 'overlay' and not overlay:
+        raise ValueError("detect_frames: `heatmap` with over='overlay' colours the overlay, so it needs overlay=True")
 
 
-def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw=None):
+def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw=None, heatmap=None):
     """`detect_frames` from the three prepared network inputs on"""
     R, B = net.resolution, len(arena.frames)
     shapes = [(f[1], f[2]) for f in arena.frames]
@@ -576,19 +698,23 @@ def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_ima
     if draw is not None:
         res['class_counts'] = torch.empty(B, len(draw.class_names), dtype=torch.int32, device=boxes.device)
         draw_detections_frames(maps['arenas']['overlay'], frames_layout(shapes), boxes, cnt, shapes, draw, (R, R), res['class_counts'])
+    if heatmap is not None:
+        under = (maps['arenas']['overlay'], frames_layout(shapes)) if heatmap.over == 'overlay' else (arena, None)
+        heat = heatmap_frames(det, shapes, under[0], under[1], heatmap, (R, R), letterbox_image)
+        res.update({k: heat[k] for k in ('heat_mask', 'heat_range', 'heatmap')})
     return res
 
 
 def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_points=512, columns=None, point_columns=None, cell=None, conf_thres=0.5, nms_thres=0.4,
                               letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE,
-                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda', draw=None):
+                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda', draw=None, heatmap=None):
     """`detect_frames` from raw radar point clouds instead of ready radar maps and sampled points: `clouds` is a list of CPU float32 / float64 arrays [n_i, F] (or
     `data.Clouds` already on the device), uploaded once.  The normalised radar map is `data.radar_maps_batch(..., normalize=True)` (the reference's offline
     rasterisation, then its min-max scaling: `columns` = the columns of range, doppler, rcs, u, v, default 0..4; `cell` default (6.0, 3.375)); the points are
     `data.radar_points_batch`: `num_points` rows per frame by `indices` [B, N] or drawn from `rng`, the columns `point_columns` (default: the first
     `net.pc_channels`), normalised.  Two launches for the map and one for the points whatever B is, nothing read back; everything else and the result as `detect_frames`."""
     from . import data as _data
-    _need_overlay(draw, overlay)
+    _need_overlay(draw, overlay, heatmap)
     R = net.resolution
     packed = _data._as_clouds(clouds, device)
     arena = _data._as_arena(frames, 3, packed.data.device, 'images')
@@ -598,4 +724,4 @@ def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_p
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = _data.radar_maps_batch(packed, R, _data.MAP_COLUMNS if columns is None else columns, _data.CELL if cell is None else cell, True, dtype)
     xp, _ = _data.radar_points_batch(packed, tuple(range(net.pc_channels)) if point_columns is None else point_columns, None, num_points, indices, rng, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap)
