@@ -13,6 +13,7 @@
 #include "k_detect.h"
 #include "k_conv3.h"
 #include "k_gemm.h"
+#include "k_lngemm.h"
 #include "k_ghost.h"
 #include "k_headdw.h"
 #include "k_mlp.h"
@@ -214,9 +215,17 @@ public:
             batch_jobs.push_back(j);
             return;
         }
-        add_op(name, [g, NT, P, ydyn](hipStream_t s) mutable {
+        // LayerNorm-prologue GEMMs of the 16-bit engines (the three patchify convs and the LayerNorm + qkv projections of EdgeNeXt-S0; k_lngemm.h): the instantiated widths
+        // read and normalise a row tile once — in registers where zsplit = 1, through LDS with the zsplit chunk slices as the waves of the tile's workgroup otherwise.
+        // Same launch, same name, same arithmetic in the same order (bit-identical); every other width and the fp32 engine keep gemm_body.
+        // (EN-GDF-PN-S0, batch 64, MI355X: the six launches together 131 -> 94 us isolated, each of them faster by 2.3 - 9.2 us, the single-chunk ds1 included; 1.497 -> 1.473 ms
+        //  per step; profiles/ln_gemm_rows_once_ops.txt, profiles/ln_gemm_rows_once_ab.txt)
+        const bool rows_once = H16E && NT == 4 && P == 1 && (o.ln || o.ln_tap) && ln_gemm_rows_has<T>(pk.K, o.ln_tap) &&
+                               (o.ln_tap ? (o.conv_k == 2 && pk.K == 4 * o.Cin) : o.conv_k == 0);
+        add_op(name, [g, NT, P, ydyn, rows_once](hipStream_t s) mutable {
             if (ydyn) g.Y = *ydyn;
-            launch_gemm<T>(g, NT, P, s);
+            if (rows_once) launch_ln_gemm_rows<T>(g, s);
+            else launch_gemm<T>(g, NT, P, s);
         }, bytes, 2.0 * double(M) * (o.conv_k > 0 && o.Creal ? double(o.conv_k * o.conv_k * o.Creal) : double(pk.K)) * pk.N, lbytes);
     }
     // ---- batching of the same layer over the detection head's pyramid levels

@@ -79,6 +79,9 @@ constexpr int GEMM_DEEP_KSTEPS = ACH_GEMM_DEEP_KSTEPS;   // k-steps from which l
 // LNTAP (round 4): conv mode with a channels-first LayerNorm of the INPUT pixels fused in — every tap of the 2x2 / stride-2 patchify convs of
 // EdgeNeXt is a different input pixel with its own mean / variance over its Cin channels (edgenext.py:29-34: LayerNorm then Conv2d); the affine
 // part is folded into the conv weights on the host.  Saves the LayerNorm launch and its tensor in front of each of the three convs.
+// This body walks the k-steps twice per N-chunk (statistics, then the k-loop, where every fragment is normalised again) and is what the fp32 engine and the
+// widths without an instantiation run; the 16-bit engines take EdgeNeXt-S0's three convs — and its LayerNorm + qkv GEMMs — through k_lngemm.h, which reads
+// and normalises a row tile once (same sums in the same order, bit-identical).
 template <class T, int NT, int P, bool DEEP = false, bool LNTAP = false>
 __device__ __forceinline__ void gemm_body(const GemmParams& p, unsigned bx, unsigned nbx, unsigned by, unsigned bz, int wave_in = -1) {
     constexpr int VEC = Store<T>::VEC;
