@@ -10,7 +10,6 @@
 #include "hostemu.h"
 #define ACH_LAUNCH(kern, grid, block, stream, ...) \
     do { (void)(stream); hostemu::launch((grid), (block), [=]() { kern(__VA_ARGS__); }); } while (0)
-#define ACH_LAUNCH_LDS(kern, grid, block, lds_bytes, stream, ...) ACH_LAUNCH(kern, grid, block, stream, __VA_ARGS__)
 #define ACH_UNROLL
 #define ACH_NO_UNROLL
 namespace ach {
@@ -23,10 +22,6 @@ struct f32x4 {
 #else
 #include <hip/hip_runtime.h>
 #define ACH_LAUNCH(kern, grid, block, stream, ...) hipLaunchKernelGGL(kern, (grid), (block), 0, (stream), __VA_ARGS__)
-// the same launch with `lds_bytes` of (unused) dynamic LDS per workgroup: an OCCUPANCY CAP — a compute unit holds at most 160 KB / lds_bytes workgroups of the
-// kernel, whatever its registers would allow.  For long-lived, register-heavy kernels on the side streams: with 3 x 152 VGPRs per SIMD the row-walking
-// head leaves the caller's stream no room on ANY compute unit for as long as it runs.
-#define ACH_LAUNCH_LDS(kern, grid, block, lds_bytes, stream, ...) hipLaunchKernelGGL(kern, (grid), (block), (lds_bytes), (stream), __VA_ARGS__)
 #define ACH_UNROLL _Pragma("unroll")
 #define ACH_NO_UNROLL _Pragma("unroll 1")
 namespace ach {
@@ -460,8 +455,6 @@ inline uint4 buf_load16(const BufRsrc& r, unsigned off) {
     if (r.bytes >= 16u && off <= r.bytes - 16u) std::memcpy(&v, r.base + off, 16);
     return v;
 }
-inline uint4 buf_load16s(const BufRsrc& r, unsigned voff, unsigned soff) { return buf_load16(r, voff + soff); }
-inline uint4 buf_load16_agent(const BufRsrc& r, unsigned off) { return buf_load16(r, off); }
 #else
 typedef __amdgpu_buffer_rsrc_t BufRsrc;
 typedef unsigned int buf_u32x4 __attribute__((ext_vector_type(4)));
@@ -470,16 +463,6 @@ __device__ __forceinline__ BufRsrc make_buf(const void* p, unsigned bytes) {
 }
 __device__ __forceinline__ uint4 buf_load16(BufRsrc r, unsigned off) {
     const buf_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, int(off), 0, 0);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-// the same load at AGENT scope (sc1: it must not be served from this compute unit's L1): data another workgroup of the running kernel wrote (k_mlpband.h run kernel)
-__device__ __forceinline__ uint4 buf_load16_agent(BufRsrc r, unsigned off) {
-    const buf_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, int(off), 0, 0x10);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-// per-lane offset + wave-uniform offset (the MUBUF soffset operand: no VALU add); the range check applies to their sum
-__device__ __forceinline__ uint4 buf_load16s(BufRsrc r, unsigned voff, unsigned soff) {
-    const buf_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, int(voff), int(soff), 0);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 #endif

@@ -269,7 +269,7 @@ public:
             } else if (j0.kind == 2) {              // fused depthwise 5x5 + pointwise layer of the head towers (k_headdw.h), one job per level
                 HeadDwParams hp;
                 std::memset(&hp, 0, sizeof(hp));
-                hp.njobs = levels; hp.shared_in = j0.shared_in; hp.dbg = head_fuse_dbg;
+                hp.njobs = levels; hp.shared_in = j0.shared_in;
                 int wg = 0;
                 for (int l = 0; l < levels; ++l) {
                     const BatchJob& j = batch_jobs[size_t(l * per_level + st)];
@@ -410,46 +410,6 @@ public:
     }
     // One launch for [depthwise kxk ->] LN -> Linear -> act -> Linear -> scale -> + resid (k_mlp.h).  Returns false when the
     // width is outside the kernel's instantiations (the caller then runs the layer-wise path).
-    // ConvEncoder blocks that took the band kernel, in plan order (index of their launch): merge_band_runs turns each run of consecutive ones — block i + 1 reads what
-    // block i wrote, same geometry, nothing else of the plan in between — into ONE persistent launch (k_mlpband.h mlp_band_run_kernel; option "mlp_band_run")
-    struct BandOp { size_t op; MlpBandParams bp; int nb, shape; };
-    std::vector<BandOp> band_ops;
-    void merge_band_runs() {
-#if !defined(ACH_HOSTEMU)
-        if constexpr (H16E) {
-            if (measuring || !mlp_band_run || use_graph) { band_ops.clear(); return; }
-            for (size_t a = 0; a < band_ops.size();) {
-                size_t e = a + 1;
-                while (e < band_ops.size() && e - a < size_t(MLPB_RUN_MAX) && band_ops[e].op == band_ops[e - 1].op + 1 && band_ops[e].shape == band_ops[a].shape && band_ops[e].nb == band_ops[a].nb &&
-                       band_ops[e].bp.m.X == band_ops[e - 1].bp.m.Y && band_ops[e].bp.bands == band_ops[a].bp.bands && band_ops[e].bp.rb == band_ops[a].bp.rb &&
-                       ops[band_ops[e].op].stream == ops[band_ops[a].op].stream && !ops[band_ops[e].op].wait && !ops[band_ops[e].op].xwait &&
-                       !ops[band_ops[e - 1].op].signal && !ops[band_ops[e - 1].op].xsignal) ++e;
-                const size_t n = e - a;
-                // (the bands of a frame must share an XCD — xcd_block: the launch's workgroups in eight equal chunks of whole frames — because the blocks hand their rows over through that L2)
-                const long nwg = long(band_ops[a].bp.bands) * band_ops[a].nb;
-                if (n >= 2 && mlp_band_run_shape(band_ops[a].shape) && nwg % 8 == 0 && (nwg / 8) % band_ops[a].bp.bands == 0) {
-                    MlpBandRunParams rp;
-                    std::memset(&rp, 0, sizeof(rp));
-                    for (size_t k = 0; k < n; ++k) rp.blk[k] = band_ops[a + k].bp;
-                    rp.n = int(n);
-                    std::vector<unsigned> zeros(size_t(band_ops[a].nb), 0u);
-                    rp.sync = static_cast<unsigned*>(up_raw(zeros.data(), zeros.size() * sizeof(unsigned)));
-                    const int nb = band_ops[a].nb, shape = band_ops[a].shape;
-                    const size_t first = band_ops[a].op, last = band_ops[e - 1].op;
-                    Op& op = ops[first];
-                    for (size_t k = first + 1; k <= last; ++k) { op.bytes += ops[k].bytes; op.layout_bytes += ops[k].layout_bytes; op.flops += ops[k].flops; }
-                    op.signal = ops[last].signal; op.xsignal = ops[last].xsignal;
-                    op.name += "..+" + std::to_string(n - 1);
-                    op.fn = [rp, nb, shape](hipStream_t s) mutable { launch_mlp_band_run<T>(rp, shape, nb, s); ++rp.epoch; };
-                    ops.erase(ops.begin() + long(first) + 1, ops.begin() + long(last) + 1);
-                    for (size_t k = e; k < band_ops.size(); ++k) band_ops[k].op -= n - 1;
-                }
-                a = e;
-            }
-        }
-#endif
-        band_ops.clear();
-    }
     bool fused_mlp(const std::string& pfx, const A& xin, const A& resid, int dw_ks, A& y) {
         if (!fuse_mlp || mlp_pick_dt(xin.C) == 0) return false;
         Lin l1 = lin(pfx + ".pwconv1.weight", pfx + ".pwconv1.bias");
@@ -538,11 +498,8 @@ public:
             MlpBandParams bp;
             bp.m = mp; bp.rb = mlp_band_rows(k1, DT, dw_ks, xin.H, xin.W);
             if (band_rows_s3 > 0 && mlp_band_shape(k1, DT, dw_ks, xin.W) == 2) bp.rb = std::min(std::min(band_rows_s3, 5), xin.H);     // (the 10 x 10 maps: 5-row bands are 128 workgroups at batch 64)
-            bp.bands = cdiv(xin.H, bp.rb); bp.dbg = mlp_band_dbg;
-            int shape = mlp_band_shape(k1, DT, dw_ks, xin.W);
-            if (shape == 1 && mlp_band_lean) shape = 11;
-            const int nb = xin.B;
-            if (!measuring) band_ops.push_back(BandOp{ops.size(), bp, nb, shape});          // (merge_band_runs: consecutive blocks of a stage as one launch)
+            bp.bands = cdiv(xin.H, bp.rb);
+            const int shape = mlp_band_shape(k1, DT, dw_ks, xin.W), nb = xin.B;
             add_op(name, [bp, nb, shape](hipStream_t s) { launch_mlp_band<T>(bp, shape, nb, s); }, bytes, flops);
             return true;
         }
@@ -580,7 +537,7 @@ public:
     // y = l2(act(l1(x))) as one launch (k_mlp.h without LayerNorm / residual); false when the widths are not instantiated
     // (`allow_split` = false: the caller's "map" is not a frame — pc_pair presents B*N points as one map, whose size depends on the BATCH; the four-waves-per-tile
     //  mode sums in another fp32 order than the one-wave mode, and a frame's result must not depend on the batch it is in)
-    bool chain2(const std::string& name, const A& x, const Lin& l1, int act, const Lin& l2, A& y, bool* planar = nullptr, bool allow_split = true) {
+    bool chain2(const std::string& name, const A& x, const Lin& l1, int act, const Lin& l2, A& y, bool allow_split = true) {
         if (!fuse_mlp) return false;
         const int Cin = x.C, hidden = l1.N, Cout = l2.N;
         const int k1 = cdiv(Cin, KC), J = cdiv(hidden, 32);
@@ -595,10 +552,6 @@ public:
         mp.X = x.p; mp.ldx = x.ld; mp.Y = y.p; mp.ldy = y.ld;
         chain_weights(mp, Cin, DT, l1, act, l2);
         mp.M = x.rows();
-        if (planar) {                            // channel-planar rows for the MFMA bilinear phase of the fused last decoder level
-            *planar = *planar && small && Cout == 16;
-            if (*planar) mp.planar_w = x.W;
-        }
         add_op(name, [mp, DT, split, small](hipStream_t s) { if (small) launch_chain<T>(mp, s); else launch_mlp<T>(mp, DT, split, s); },
                double(mp.M) * (Cin + Cout) * sizeof(T), 2.0 * double(mp.M) * hidden * (Cin + Cout));
         return true;
@@ -896,7 +849,6 @@ public:
             }
             if (has_preset) throw AchError{ACH_ERR_INVALID, "stage output destination was not consumed"};
             feats[i] = x;
-            merge_band_runs();
             reached(Point(kPtStage0 + i));
         }
     }
@@ -1314,11 +1266,6 @@ public:
         y0 = alloc(x.B, x.H, x.W, x.C);
         y1 = alloc(x.B, x.H, x.W, x.C);
         SaApplyParams pa{x.p, x.ld, y0.p, y1.p, y0.ld, coef, x.B, x.H * x.W, x.C};
-        if (sa_fuse && x.C <= 256 && (long(x.H) * x.W * x.C) % 256 == 0) {       // the coefficients in the apply launch (k_nhwc.h): bit-identical, one launch fewer
-            SaFusedParams pf{pc, pa};
-            ew(pfx0 + ".coef+apply", sa_apply_fused_kernel<T>, pf, x.rows() * x.C, 3.0 * x.rows() * x.C * sizeof(T));
-            return;
-        }
         ew(pfx0 + ".coef", sa_coef_kernel, pc, long(2) * x.B * x.C);
         if (x.C % 8 == 0 && x.ld % 4 == 0 && y0.ld % 8 == 0) ew(pfx0 + ".apply", sa_apply8_kernel<T>, pa, x.rows() * (x.C / 8), 3.0 * x.rows() * x.C * sizeof(T));
         else ew(pfx0 + ".apply", sa_apply_kernel<T>, pa, x.rows() * x.C, 3.0 * x.rows() * x.C * sizeof(T));
@@ -1386,30 +1333,6 @@ public:
         UpGhostParams p{t.p, t.ld, y.p, y.ld, up_f32(wt), up_f32(sh), x.B, x.H, x.W, Cg};
         const dim3 grid(unsigned(cdiv(2 * x.W, UPG_TS)) * unsigned(cdiv(2 * x.H, UPG_TS)) * unsigned(x.B)), block(unsigned(16 * Cg));
         const double bytes = double(t.rows()) * Cg * sizeof(T) + double(y.rows()) * cout * sizeof(T);
-        if constexpr (H16E) if (level_rows && (Cg == 16 || Cg == 24 || Cg == 32) && t.ld % 2 == 0 && y.ld % 2 == 0 &&
-            double(y.rows()) * y.ld * sizeof(T) < 2147483648.0) {
-            // row-walking form (k_dechead.h; option level_rows, OFF: measured slower than the LDS tile on these write-bound levels — 34 / 60 us against 25 / 48)
-            const int H2 = 2 * x.H, band = std::max(8, std::min(head_band, H2));
-            UpGhostRowsParams rp{t.p, t.ld, y.p, y.ld, p.Wdw, p.bdw, x.B, x.H, x.W, Cg, x.W > 0 ? float(x.W - 1) / float(2 * x.W - 1) : 0.f,
-                                 band, cdiv(H2, band), cdiv(2 * x.W, UGR_VALID)};
-            const float sy = x.H > 0 ? float(x.H - 1) / float(2 * x.H - 1) : 0.f;
-            std::vector<DecHeadRow> rg(static_cast<size_t>(H2) + 4);
-            for (int i = 0; i < H2 + 4; ++i) {
-                const float fy = sy * float(i < H2 ? i : H2 - 1);
-                int y0 = int(fy);
-                if (y0 > x.H - 1) y0 = x.H - 1;
-                rg[size_t(i)] = DecHeadRow{y0, y0 < x.H - 1 ? fy - float(y0) : 0.f};
-            }
-            const DecHeadRow* rows = static_cast<const DecHeadRow*>(up_raw(rg.data(), rg.size() * sizeof(DecHeadRow)));
-            const dim3 rgrid(unsigned(rp.strips) * unsigned(rp.bands) * unsigned(x.B)), rblock(64);
-            const int np = Cg / 8;
-            add_op(ghost_pfx + ".upghost", [rp, rgrid, rblock, rows, np](hipStream_t s) {
-                if (np == 2) ACH_LAUNCH((upghost_rows_kernel<T, 2>), rgrid, rblock, s, rp, rows);
-                else if (np == 3) ACH_LAUNCH((upghost_rows_kernel<T, 3>), rgrid, rblock, s, rp, rows);
-                else ACH_LAUNCH((upghost_rows_kernel<T, 4>), rgrid, rblock, s, rp, rows);
-            }, bytes);
-            return y;
-        }
         if (Cg == 16) add_op(ghost_pfx + ".upghost", [p, grid, block](hipStream_t s) { ACH_LAUNCH((upghost_kernel<T, 16>), grid, block, s, p); }, bytes);
         else if (Cg == 24) add_op(ghost_pfx + ".upghost", [p, grid, block](hipStream_t s) { ACH_LAUNCH((upghost_kernel<T, 24>), grid, block, s, p); }, bytes);
         else if (Cg == 32) add_op(ghost_pfx + ".upghost", [p, grid, block](hipStream_t s) { ACH_LAUNCH((upghost_kernel<T, 32>), grid, block, s, p); }, bytes);
@@ -1426,17 +1349,13 @@ public:
         Lin lh = conv_bn(head_pfx + ".primary_conv.0", head_pfx + ".primary_conv.1", 1e-5);
         if (Cg != UGH_CG || 2 * Cg != cout || lh.K != cout || lh.N != init || init > UGH_IMAX) throw AchError{ACH_ERR_UNSUPPORTED, head_pfx + ": fused last level expects 16+16 channels"};
         A t;
-        // bf16: bilinear phase on the matrix cores, t channel-planar (upghost_head_mfma_kernel)
-        bool planar = !t_in && head_mfma && std::is_same<T, bf16_t>::value && x.W % 4 == 0 && size_t(x.B) * x.H * x.W * Cg * sizeof(T) < (size_t(1) << 31);
         if (t_in) t = *t_in;
-        else if (!chain2(ghost_pfx + ".lowres_pair", x, lu, ACT_RELU, lp, t, &planar)) {
-            planar = false;
+        else if (!chain2(ghost_pfx + ".lowres_pair", x, lu, ACT_RELU, lp, t)) {
             A u = alloc(x.B, x.H, x.W, lu.N);
             { GemmOpt o; o.act = ACT_RELU; gemm(up_pfx + ".conv", x, pack(lu), u, o); }
             t = alloc(x.B, x.H, x.W, Cg);
             gemm(ghost_pfx + ".primary_lowres", u, pack(lp), t);
         }
-        if (planar) aalloc(256);                  // the MFMA head's 16-byte window loads may start in the last row's last 16 bytes
         auto dw_fold = [&](const std::string& pfx, int n, std::vector<float>& wt, std::vector<float>& bias) {
             const HostTensor& w = W(pfx + ".cheap_operation.0.weight");
             std::vector<float> sc, sh; bn_coeffs(pfx + ".cheap_operation.1", 1e-5, sc, sh);
@@ -1455,7 +1374,7 @@ public:
         const double bytes = double(t.rows()) * Cg * sizeof(T) + 4.0 * double(t.rows()) * oup * sizeof(T);
         // (the row walk addresses one SAMPLE at a time — a 64-bit base per frame, 32-bit byte offsets inside it — so only a frame's own tensors must stay below
         //  2 GiB, whatever the batch: round 4's test was on the whole batch and dropped plans above ~145 frames back to the LDS-tile head)
-        if constexpr (H16E) if (head_rows && !planar && t.ld % 4 == 0 && double(x.H) * x.W * t.ld * sizeof(T) < 2147483648.0 &&
+        if constexpr (H16E) if (head_rows && t.ld % 4 == 0 && double(x.H) * x.W * t.ld * sizeof(T) < 2147483648.0 &&
                                 4.0 * double(x.H) * x.W * oup * sizeof(T) < 2147483648.0 && double(x.B) * cdiv(2 * x.H, 8) * cdiv(2 * x.W, DH_VALID) < 4294967296.0) {
             // row-walking kernel (k_dechead.h): head 1x1 as the A fragment of v_mfma_f32_16x16x32_bf16 — D row 4g + r = head channel g + 4r,
             // k = 8g + j = channel 4g + j of x1 (j < 4) or of x2 (j >= 4) — biases and the head's depthwise filters indexed by head channel
@@ -1486,66 +1405,32 @@ public:
                 rg[size_t(i)] = DecHeadRow{y0, y0 < x.H - 1 ? fy - float(y0) : 0.f};
             }
             const DecHeadRow* rows = static_cast<const DecHeadRow*>(up_raw(rg.data(), rg.size() * sizeof(DecHeadRow)));
-            const int dbg = head_debug;
             const bool dw2 = nch > 4, tapf = full_taps;
             const bool alt = io_alt();
-            const unsigned pad = unsigned(head_lds_pad);          // occupancy cap of the row-walking head (option "head_lds_pad", bytes of unused dynamic LDS per single-wave workgroup)
-            add_op(head_pfx + ".upghost_head", [dp, grid, block, out, dbg, dw2, tapf, rows, two, alt, pad](hipStream_t s) mutable {
+            add_op(head_pfx + ".upghost_head", [dp, grid, block, out, dw2, tapf, rows, two, alt](hipStream_t s) mutable {
                 dp.out = *out;
                 auto go = [&](auto io_tag) {             // IO: the type of the caller's output tensor
                     using IO = decltype(io_tag);
                     if (two) {
                         if (tapf) { if (dw2) ACH_LAUNCH((dechead_rows2_kernel<T, IO, true, true>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows2_kernel<T, IO, false, true>), grid, block, s, dp, rows); }
-                        else { if (dw2) ACH_LAUNCH_LDS((dechead_rows2_kernel<T, IO, true, false>), grid, block, pad, s, dp, rows); else ACH_LAUNCH_LDS((dechead_rows2_kernel<T, IO, false, false>), grid, block, pad, s, dp, rows); }
+                        else { if (dw2) ACH_LAUNCH((dechead_rows2_kernel<T, IO, true, false>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows2_kernel<T, IO, false, false>), grid, block, s, dp, rows); }
                         return;
                     }
                     if (tapf) {                      // parity-test plans: the variant that also writes [x1 | x2]
-                        if (dw2) ACH_LAUNCH((dechead_rows_kernel<T, IO, true, true, 0>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows_kernel<T, IO, false, true, 0>), grid, block, s, dp, rows);
+                        if (dw2) ACH_LAUNCH((dechead_rows_kernel<T, IO, true, true>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows_kernel<T, IO, false, true>), grid, block, s, dp, rows);
                         return;
                     }
-#define ACH_DH_CASE(D) case D: if (dw2) ACH_LAUNCH((dechead_rows_kernel<T, IO, true, false, D>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows_kernel<T, IO, false, false, D>), grid, block, s, dp, rows); break;
-#if defined(ACH_HEAD_DEBUG)
-                    switch (dbg) { ACH_DH_CASE(1) ACH_DH_CASE(2) ACH_DH_CASE(3) ACH_DH_CASE(4) ACH_DH_CASE(7) ACH_DH_CASE(8) ACH_DH_CASE(15) default: ACH_DH_CASE(0) }
-#else
-                    switch (dbg) { default: ACH_DH_CASE(0) }
-#endif
-#undef ACH_DH_CASE
+                    if (dw2) ACH_LAUNCH((dechead_rows_kernel<T, IO, true, false>), grid, block, s, dp, rows); else ACH_LAUNCH((dechead_rows_kernel<T, IO, false, false>), grid, block, s, dp, rows);
                 };
                 if (alt) go(IOB{}); else go(T{});
             }, bytes, 2.0 * double(t.rows()) * 4.0 * cout * init);
             return;
         }
         const dim3 block(UGH_THREADS);
-        if constexpr (std::is_same<T, bf16_t>::value) if (planar) {
-            const int tw = 16 * UGM_NSEG - 4;
-            const unsigned tiles = unsigned(cdiv(2 * x.W, tw)) * unsigned(cdiv(2 * x.H, UGM_TH)) * unsigned(x.B);
-            const unsigned cap = head_grid > 0 ? unsigned(head_grid) : (UGM_GRID > 0 ? unsigned(UGM_GRID) : tiles);
-            const dim3 grid(tiles < cap ? tiles : cap);
-            const int dbg = head_debug;
-            add_op(head_pfx + ".upghost_head", [p, grid, block, out, dbg, tiles](hipStream_t s) mutable {
-                p.out = *out;
-#define ACH_UGM_CASE(D) case D: if (grid.x < tiles) ACH_LAUNCH((upghost_head_mfma_kernel<UGM_NSEG, UGM_TH, true, D>), grid, block, s, p, p.Wdw, p.bdw, p.Wh, p.bh, p.Wdh, p.bdh); \
-                             else ACH_LAUNCH((upghost_head_mfma_kernel<UGM_NSEG, UGM_TH, false, D>), grid, block, s, p, p.Wdw, p.bdw, p.Wh, p.bh, p.Wdh, p.bdh); break;
-#if defined(ACH_HEAD_DEBUG)
-                switch (dbg) { ACH_UGM_CASE(1) ACH_UGM_CASE(3) ACH_UGM_CASE(7) ACH_UGM_CASE(14) ACH_UGM_CASE(15) default: ACH_UGM_CASE(0) }
-#else
-                switch (dbg) { default: ACH_UGM_CASE(0) }
-#endif
-#undef ACH_UGM_CASE
-            }, bytes);
-            return;
-        }
         const dim3 grid(unsigned(cdiv(2 * x.W, UGH_TW)) * unsigned(cdiv(2 * x.H, UGH_TH)) * unsigned(x.B));
-        const int dbg = head_debug;
-        add_op(head_pfx + ".upghost_head", [p, grid, block, out, dbg](hipStream_t s) mutable {
+        add_op(head_pfx + ".upghost_head", [p, grid, block, out](hipStream_t s) mutable {
             p.out = *out;
-#define ACH_UGH_CASE(D) case D: ACH_LAUNCH((upghost_head_kernel<T, D>), grid, block, s, p, p.Wdw, p.bdw, p.Wh, p.bh, p.Wdh, p.bdh); break;
-#if defined(ACH_HEAD_DEBUG)
-            switch (dbg) { ACH_UGH_CASE(1) ACH_UGH_CASE(3) ACH_UGH_CASE(7) ACH_UGH_CASE(14) ACH_UGH_CASE(15) default: ACH_UGH_CASE(0) }
-#else
-            switch (dbg) { default: ACH_UGH_CASE(0) }
-#endif
-#undef ACH_UGH_CASE
+            ACH_LAUNCH((upghost_head_kernel<T>), grid, block, s, p, p.Wdw, p.bdw, p.Wh, p.bh, p.Wdh, p.bdh);
         }, bytes);
     }
 
@@ -2070,7 +1955,7 @@ public:
         if (pc_chain && act2 == ACT_NONE && x.rows % 16 == 0) {
             A xa; xa.p = x.p; xa.B = 1; xa.H = int(x.rows / 16); xa.W = 16; xa.C = x.C; xa.ld = x.ld;
             A ya;
-            if (chain2(n1 + "+" + n2.substr(n2.rfind('.') + 1), xa, l1, act1, l2, ya, nullptr, false)) { Rows y; y.p = ya.p; y.rows = x.rows; y.C = ya.C; y.ld = ya.ld; return y; }
+            if (chain2(n1 + "+" + n2.substr(n2.rfind('.') + 1), xa, l1, act1, l2, ya, false)) { Rows y; y.p = ya.p; y.rows = x.rows; y.C = ya.C; y.ld = ya.ld; return y; }
         }
         return pc_layer(n2, pc_layer(n1, x, l1, act1), l2, act2);
     }

@@ -54,7 +54,6 @@ struct MlpParams {
     const void* W2; const float* b2;      // [C][hidden] packed as ONE chunk of DT tiles with J * (8 / VEC) k-steps ; bias padded to 16 * DT
     long M; int C, k1, J, act; float ln_eps;
     int ln, Cout;                         // ln = 0: no normalisation (plain two-layer chain); Cout: output width (R may be null)
-    int planar_w;                         // chain_kernel only, > 0: Y is written channel-planar per map row, [M / planar_w][Cout][planar_w]
     int dw_even;                          // SPLIT + depthwise: the k1 * dw_k tap ROWS are dealt evenly to the four waves (mlp_inputs), not whole k-steps
     void* Hout; long ldh;                 // chain_kernel only, optional: the hidden activations act(W1 x + b1) are stored too (rows of ldh elements) — a layer pair whose FIRST output is needed as well (k_csphead.h's [u | v])
 };
@@ -744,14 +743,7 @@ __global__ ACH_CHAIN_BOUNDS void chain_kernel(const MlpParams p) { f16_sat_mode<
             float o[8];
             ACH_UNROLL
             for (int r = 0; r < 4; ++r) { o[r] = acc[0][r] + b2[r]; o[4 + r] = acc[1][r] + b2[4 + r]; }
-            if (p.planar_w > 0) {                       // [row][channel][x]: the layout upghost_head_mfma_kernel's A operand wants
-                const long row = mr / p.planar_w;
-                T* yo = static_cast<T*>(p.Y) + (row * p.Cout + nb) * p.planar_w + (mr - row * p.planar_w);
-                ACH_UNROLL
-                for (int i = 0; i < 8; ++i) Store<T>::st(yo + long(i) * p.planar_w, o[i]);
-            } else {
-                Store<T>::st8(static_cast<T*>(p.Y) + mr * p.ldy + nb, o);
-            }
+            Store<T>::st8(static_cast<T*>(p.Y) + mr * p.ldy + nb, o);
         }
     }
 }

@@ -26,7 +26,6 @@ namespace ach {
 struct MlpBandParams {
     MlpParams m;
     int rb, bands;               // rows per band, bands per frame
-    int dbg;                     // timing experiments only (option mlp_band_dbg; results are wrong): bit 0 no staging, 1 no depthwise, 2 no LayerNorm, 3 no MLP, 4 no reduction
 };
 
 constexpr int MLPB_SP = 5;       // strip of output pixels per thread in the depthwise phase
@@ -52,9 +51,8 @@ struct MlpBandGeom {
 // PREF: the next hidden chunk's weight fragments are requested one chunk ahead (a second register set).
 // TILEPAR (the narrow blocks of the large maps: few hidden chunks, many tiles): a wave takes whole TILES (t = wave, wave + 8, ...) through
 // every hidden chunk instead of a share of the chunks for every tile — no partial sums, no reduction phase.
-// the block for (frame b, band) of `bp`, on the workgroup's two LDS arrays (the kernel below; mlp_band_run_kernel calls it once per block of a run)
-// COH: the input rows may have been written by OTHER workgroups of the running launch (the run kernel): the halo loads go to L2 (agent scope), not to this unit's L1
-template <class T, int K1, int DT, int KS, int RB, int MAXW, bool XF32, bool PREF, bool TILEPAR, bool COH = false>
+// the block for (frame b, band) of `bp`, on the workgroup's two LDS arrays (the kernel below)
+template <class T, int K1, int DT, int KS, int RB, int MAXW, bool XF32, bool PREF, bool TILEPAR>
 __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int band, const int b, float* xin, float* dwv) {
     using G = MlpBandGeom<K1, DT, KS, RB, MAXW, XF32>;
     constexpr int CP = G::CP, NT = G::NT, SP = MLPB_SP, NTB = mlpb_ntb(DT, XF32);
@@ -69,10 +67,11 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
     const int npx = rows * W, nt = (npx + 15) / 16;
     const int WCr = W + KS - 1, HRr = rows + KS - 1;
     const T* X = static_cast<const T*>(p.X) + long(b) * H * W * p.ldx;
-    const BufRsrc xcoh = make_buf(X, COH ? unsigned(long(H) * W * p.ldx * long(sizeof(T))) : 0u);       // (one frame: far below 2 GiB)
 
     // ---- 0. halo tile -> LDS (fp32), zero outside the map and beyond the real channels
-    if (!(bp.dbg & 1)) {
+    // (phases 0 and 1 each stand under a test that always holds — a band has at least one row: as straight-line code the compiler computes phase 1's scalars in
+    //  front of phase 0 and keeps them through it, and the kernel, which has no SGPR to spare, spills 5 - 18 more of them to VGPR lanes: measured -0.9 % on EN-S2)
+    if (HRr > 0) {
         constexpr int C8 = CP / 8;
         const int total = HRr * WCr * C8;
         constexpr int UN = 4;                                              // loads in flight per thread
@@ -86,8 +85,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
                     const int c8 = it % C8, pos = it / C8, wc = pos % WCr, hr = pos / WCr;
                     const int iy = y0 - KS / 2 + hr, ix = wc - KS / 2;
                     if (iy >= 0 && iy < H && ix >= 0 && ix < W && c8 * 8 < C) {
-                        if (COH && !(bp.dbg & 64)) raw[u] = buf_load16_agent(xcoh, unsigned(((long(iy) * W + ix) * p.ldx + c8 * 8) * long(sizeof(T))));
-                        else raw[u] = *reinterpret_cast<const uint4*>(X + (long(iy) * W + ix) * p.ldx + c8 * 8);
+                        raw[u] = *reinterpret_cast<const uint4*>(X + (long(iy) * W + ix) * p.ldx + c8 * 8);
                     }
                 }
             }
@@ -110,7 +108,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
     }
     __syncthreads();
     // ---- 1. depthwise k x k from LDS: thread = strip of SP pixels x 4 channels
-    if (!(bp.dbg & 2)) {
+    if (rows > 0) {
         constexpr int C4 = CP / 4;
         const int nstrip = (W + SP - 1) / SP, total = rows * nstrip * C4;
         for (int it = tid; it < total; it += MLPB_THREADS) {
@@ -150,7 +148,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
     }
     __syncthreads();
     // ---- 2. LayerNorm per pixel (affine folded into W1 / b1), rows -> MFMA B fragments in LDS
-    for (int t = wave; t < ((bp.dbg & 4) ? 0 : nt); t += MLPB_THREADS / 64) {
+    for (int t = wave; t < nt; t += MLPB_THREADS / 64) {
         const int pix = t * 16 + px;
         const bool valid = pix < npx;
         float v[K1][8];
@@ -190,7 +188,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
         for (int k = 0; k < NTW; ++k) { const int t = wave + k * (MLPB_THREADS / 64); ACH_UNROLL for (int s = 0; s < K1; ++s) xf[k][s] = xs[((t < nt ? t : 0) * K1 + s) * 64 + lane]; }
         const uint4* W1f = static_cast<const uint4*>(p.W1) + lane;
         const uint4* W2f = static_cast<const uint4*>(p.W2) + lane;
-        if (wave < nt && !(bp.dbg & 8))
+        if (wave < nt)
         for (int j = 0; j < p.J; ++j) {
             uint4 w1[K1][2], w2[DT];
             const uint4* w1p = W1f + long(j) * K1 * 2 * 64;
@@ -220,7 +218,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
         ACH_UNROLL
         for (int k = 0; k < NTW; ++k) {
             const int t = wave + k * (MLPB_THREADS / 64), pix = t * 16 + px;
-            if (t >= nt || pix >= npx || (bp.dbg & 16)) continue;
+            if (t >= nt || pix >= npx) continue;
             const long m = long(y0) * W + pix;
             ACH_UNROLL
             for (int pair = 0; pair < DT / 2; ++pair) {
@@ -254,7 +252,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
             for (int d = 0; d < DT; ++d) c[d] = W2f[(long(j) * DT + d) * 64];
         };
         if (PREF && cw < p.J) fetch(cw, n1, n2);
-        for (int j = cw; j < ((bp.dbg & 8) ? 0 : p.J); j += 4) {
+        for (int j = cw; j < p.J; j += 4) {
             if (PREF) {
                 ACH_UNROLL
                 for (int s = 0; s < K1; ++s) { w1[s][0] = n1[s][0]; w1[s][1] = n1[s][1]; }
@@ -290,7 +288,7 @@ __device__ __forceinline__ void mlp_band_body(const MlpBandParams& bp, const int
     // a round covers NTB consecutive tiles t = tb .. tb + NTB - 1; tile t lives in acc2[t / 2] of the waves of half t % 2
     ACH_UNROLL
     for (int tb = 0; tb < NT; tb += NTB) {
-        if (tb >= nt || (bp.dbg & 16)) continue;                           // (uniform)
+        if (tb >= nt) continue;                                            // (uniform)
         __syncthreads();                                                   // xs (round 0) / the previous round's sums are dead
         ACH_UNROLL
         for (int k = 0; k < NTB; ++k) {
@@ -335,65 +333,6 @@ __global__ __launch_bounds__(MLPB_THREADS, 1) void mlp_band_kernel(const MlpBand
     mlp_band_body<T, K1, DT, KS, RB, MAXW, XF32, PREF, TILEPAR>(bp, int(wg % unsigned(bp.bands)), int(wg / unsigned(bp.bands)), xin, dwv);
 }
 
-// ------------------------------------------------------------------------------------------ a RUN of blocks as one launch (round 5)
-// A stage's ConvEncoder blocks are the same kernel on the same geometry, each reading what the previous one wrote — five launches at 20 x 20 (EdgeNeXt-S0 stage 2; nine
-// on S2), each of which needs an EMPTY compute unit per workgroup (2 x 238 VGPRs per SIMD, 153 KB of LDS).  In the pipelined step the side streams' workgroups take every
-// unit a finished block frees, and each of the five launches waits again: 58 / 53 / 72 / 49 / 30 us in-step against 26 - 27 alone.  Here ONE launch runs the
-// whole run: a workgroup keeps its compute unit and its (frame, band) for all blocks; between two blocks the bands of a FRAME (the only workgroups whose halo rows it reads)
-// meet at a counter in global memory — release fence, one atomic add per workgroup, a bounded spin, acquire fence (which also drops the stale L1 lines of the
-// neighbours' rows).  The frame's workgroups sit on one XCD (xcd_block), so the traffic stays in that L2.  Deadlock-free: a workgroup that is not resident yet holds nothing,
-// and the resident ones wait only for workgroups of their own launch, which the dispatcher places as other kernels' workgroups retire; the spin is BOUNDED all the same
-// (a wrong result is a failed test, a hung GPU is a lost box).  `epoch` (the launch's sequence number, from the host) makes the counters monotonic: no reset launch.
-constexpr int MLPB_RUN_MAX = 9;
-struct MlpBandRunParams {
-    MlpBandParams blk[MLPB_RUN_MAX];
-    int n;
-    unsigned* sync;              // [frames], zero when the plan is built
-    unsigned epoch;
-};
-#if !defined(ACH_HOSTEMU)
-template <class T, int K1, int DT, int KS, int RB, int MAXW, bool XF32, bool PREF>
-__global__ __launch_bounds__(MLPB_THREADS, 1) void mlp_band_run_kernel(const MlpBandRunParams rp) { f16_sat_mode<T>();
-    using G = MlpBandGeom<K1, DT, KS, RB, MAXW, XF32>;
-    __shared__ float xin[G::XIN_FLOATS];
-    __shared__ float dwv[G::DWV_FLOATS];
-    const unsigned wg = xcd_block(blockIdx.x, gridDim.x);
-    const int bands = rp.blk[0].bands;
-    const int band = int(wg % unsigned(bands)), b = int(wg / unsigned(bands));
-    ACH_NO_UNROLL
-    for (int i = 0; i < rp.n; ++i) {
-        mlp_band_body<T, K1, DT, KS, RB, MAXW, XF32, PREF, false, true>(rp.blk[i], band, b, xin, dwv);        // (one instantiation: the first block's agent-scope loads are merely unnecessary)
-        if (i + 1 == rp.n) break;
-        // AGENT-scope release / acquire (round 6): the rows must be visible to workgroups on OTHER compute units.  Round 5 used workgroup-scope fences on the argument
-        // that a frame's workgroups share an XCD's L2 (xcd_block) — but a workgroup-scope fence is not an acquire for another unit's data and workgroup -> XCD placement
-        // is not architecturally defined; it passed the bit-identity test and was a placement-dependent protocol all the same.  The agent-scope
-        // form costs the L2 write-back / invalidate (measured in round 5: 41.5 k -> 37.8 k frames/s), which is why the option stays OFF: kept as the correct statement
-        // of the experiment, not as a plan anyone should select.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if (threadIdx.x == 0 && !(rp.blk[0].dbg & 32)) {          // (dbg 32 / 64: timing experiments — no barrier / plain halo loads; wrong results)
-            const unsigned target = (rp.epoch * unsigned(rp.n - 1) + unsigned(i + 1)) * unsigned(bands);
-            __hip_atomic_fetch_add(rp.sync + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int spin = 0; spin < (1 << 22); ++spin) {
-                if (int(__hip_atomic_load(rp.sync + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) break;
-                __builtin_amdgcn_s_sleep(8);
-            }
-        }
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-}
-template <class T>
-inline bool launch_mlp_band_run(const MlpBandRunParams& rp, int shape, int B, hipStream_t stream) {
-    const dim3 grid(unsigned(rp.blk[0].bands) * unsigned(B)), block(MLPB_THREADS);
-    if (shape == 1) ACH_LAUNCH((mlp_band_run_kernel<T, 3, 6, 7, 5, 20, true, true>), grid, block, stream, rp);
-    else if (shape == 3) ACH_LAUNCH((mlp_band_run_kernel<T, 5, 10, 7, 4, 20, false, false>), grid, block, stream, rp);
-    else return false;
-    return true;
-}
-#endif
-inline bool mlp_band_run_shape(int shape) { return shape == 1 || shape == 3; }
-
 // the instantiated shapes (k-steps of the input, output tiles, kernel size, rows per band, widest map):
 //   d =  96, 7x7, maps up to 20 wide (EdgeNeXt-S0 stage 2): fp32 halo tile, 5 rows, weights prefetched
 //   d = 176, 9x9, maps up to 10 wide (EdgeNeXt-S0 stage 3): bf16 halo tile, 5 rows
@@ -413,7 +352,6 @@ template <class T>
 inline void launch_mlp_band(const MlpBandParams& bp, int shape, int B, hipStream_t stream) {
     const dim3 grid(unsigned(bp.bands) * unsigned(B)), block(MLPB_THREADS);
     if (shape == 1) ACH_LAUNCH((mlp_band_kernel<T, 3, 6, 7, 5, 20, true, true>), grid, block, stream, bp);
-    else if (shape == 11) ACH_LAUNCH((mlp_band_kernel<T, 3, 6, 7, 5, 20, false, false>), grid, block, stream, bp);      // option mlp_band_lean: 16-bit halo tile, no weight prefetch set
     else if (shape == 2) ACH_LAUNCH((mlp_band_kernel<T, 6, 12, 9, 5, 10, false, false>), grid, block, stream, bp);
     else if (shape == 3) ACH_LAUNCH((mlp_band_kernel<T, 5, 10, 7, 4, 20, false, false>), grid, block, stream, bp);
     else if (shape == 4) ACH_LAUNCH((mlp_band_kernel<T, 2, 4, 5, 4, 40, true, false, true>), grid, block, stream, bp);

@@ -157,18 +157,8 @@ int ach_load_weights(ach_handle* h, const ach_tensor_desc* tensors, size_t n);
  *   "xca_slice"         integer, default 0 (64, 128 on maps of 1024 tokens or more): with xca_frame, tokens per workgroup of the front kernel
  *   "xca_front_waves"   4 / 8 / 16, default 0 (by the number of work units): with xca_frame, waves per workgroup of the front kernel
  *   "xca_back_waves"    4 / 8 / 16, default 0 (by the number of work units): with xca_frame, waves per workgroup of the back kernel
- *   "sa_fuse"           0 / 1, default 0 (round 4): ShuffleAttention's coefficient launch folded into the apply launch — measured slower
- *   "level_rows"        0 / 1, default 0 (round 3, 16-bit engines): decoder levels as row-walking kernels — measured slower
- *   "head_mfma"         0 / 1, default 0: bilinear phase of the fused segmentation head on MFMA — measured slower
- *   "head_grid"         integer, default 0 (= the kernel's own grid): persistent workgroups of the MFMA head kernel
- *   "head_lds_pad"      0..65536 (clamped), default 0 (round 5): bytes of unused dynamic LDS per workgroup of the Ghost-FPN row-walking head = an occupancy cap; every cap measured slower
- *   "mlp_band_run"      0 / 1, default 0 (round 5): a stage's band-kernel ConvEncoder blocks as one persistent launch with per-frame barriers; bit-identical, measured no faster
- *   "mlp_band_lean"     integer, default 0 (round 6): the d = 96 band kernel with a 16-bit halo tile, 98 KB of LDS: measured neutral
  * Debugging only
- *   "xwait2_op"         launch index, default -1 (none): pipelined mode, the launch that waits for the previous forward's decoders instead of the planned one
- *   "head_debug"        integer, default 0: phase-kill timing variant of the fused last decoder level, WRONG results
- *   "mlp_band_dbg"      integer, default 0: phase-kill timing variant of the band kernel, WRONG results
- *   "head_fuse_dbg"     integer, default 0: phase-kill timing variant of the fused head layer, WRONG results */
+ *   "xwait2_op"         launch index, default -1 (none): pipelined mode, the launch that waits for the previous forward's decoders instead of the planned one */
 int ach_set_option(ach_handle* h, const char* key, int32_t value);
 int ach_get_option(const ach_handle* h, const char* key, int32_t* value);
 const char* ach_option_key(int32_t index);

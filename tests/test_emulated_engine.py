@@ -380,36 +380,6 @@ def test_emulated_fused_mv2_blocks_agree_with_the_three_launches(dtype, tol):
         assert rel_err(a, b) < tol
 
 
-@pytest.mark.parametrize('res,batch', [(128, 1), (96, 2)])
-def test_emulated_mfma_bilinear_head_agrees_with_the_per_position_kernel(res, batch):
-    """bf16: the fused last decoder level with its bilinear phase on the matrix cores (upghost_head_mfma_kernel: channel-planar t from
-    chain_kernel, interpolation weights split hi + lo so the product is exact to 2^-17) against the per-position gather kernel.  Both end
-    in the same fp32 tail, so the segmentation outputs and the `lane.1_to_0` / `se.1_to_0` taps may differ by a bf16 rounding flip at most.
-    128: ragged 12x16 tiles in x; 96: ragged in x and y, two frames."""
-    from achelous_amd.engine import NativeEngine
-    kw, sd, (x, xr, xp) = _setup('en_s0', res, batch, 16)
-    td = torch.bfloat16
-    outs = []
-    for v in (1, 0):
-        eng = NativeEngine(emu_library(), num_det=kw['num_det'], num_seg=kw['num_seg'], phi=kw['phi'], backbone=kw['backbone'],
-                           resolution=kw['resolution'], pc_channels=kw['pc_channels'], pc_classes=kw['pc_classes'],
-                           num_points=16, nano_head=kw['nano_head'], spp=kw['spp'], dtype=DTYPE_BF16)
-        eng.set_option('head_mfma', v)
-        eng.set_option('head_rows', 0)                                # both kernels of this test keep [x1 | x2] in fp32 through the head's 1x1 (the row-walking default rounds it to bf16)
-        eng.set_option('head_grid', 8 if res == 128 else 5)          # persistent workgroups walk several tiles each (XCD split / plain stride)
-        eng.set_option('full_taps', 1)
-        eng.load_state_dict(sd)
-        eng.plan(batch)
-        o = alloc_outputs(kw, batch, 16, td, 'cpu')
-        eng.forward(x.to(td), xr.to(td), xp.to(td), o)
-        outs.append({'se': o[3].float(), 'lane': o[4].float(), 'lane.1_to_0': eng.read_tap('lane.1_to_0'), 'se.1_to_0': eng.read_tap('se.1_to_0')})
-    for k in outs[0]:
-        a, b = outs[0][k], outs[1][k]
-        assert a.shape == b.shape
-        assert rel_err(a, b) < 1e-2, (k, rel_err(a, b))
-        assert float((a != b).float().mean()) < 0.05, (k, float((a != b).float().mean()))
-
-
 @pytest.mark.parametrize('dtype', [DTYPE_F32, DTYPE_BF16])
 @pytest.mark.parametrize('cells', [0, 2, 40, -1])
 def test_emulated_radar_skip_is_bit_identical(dtype, cells):
@@ -545,8 +515,7 @@ def test_emulated_row_walking_head_matches_the_tile_kernel(name, res, band, num_
     """bf16 engine: the row-walking fused last decoder level (k_dechead.h, option head_rows = 1, default) against the LDS tile kernel
     (head_rows = 0) and the oracle.  Bands of 8 rows put a band boundary inside every window phase; 96 / 64 / 128 columns end in partial
     strips (96 = 8 x 12, 64 = 5 x 12 + 4, 128 = 10 x 12 + 8); num_seg = 13 (init 7, 6 cheap channels) uses both accumulators of a lane
-    group.  The two kernels differ only in where [x1 | x2] is rounded to bf16.  Option level_rows moves the other two decoder levels to their
-    row-walking kernel (upghost_rows_kernel: 24 + 24 and 16 + 16 channels on EN-S0, 32 + 32 and 16 + 16 on EN-S2); their taps are compared too."""
+    group.  The two kernels differ only in where [x1 | x2] is rounded to bf16."""
     kw, sd, (x, xr, xp) = _setup(name, res, 2, 16)
     if num_seg != kw['num_seg']:
         from achelous_amd.nets import Achelous
@@ -562,7 +531,6 @@ def test_emulated_row_walking_head_matches_the_tile_kernel(name, res, band, num_
                            pc_channels=kw['pc_channels'], pc_classes=kw['pc_classes'], num_points=16, nano_head=True, spp=True, dtype=sdt[0])
         eng.set_option('full_taps', 1)
         eng.set_option('head_rows', rows)
-        eng.set_option('level_rows', 1 if rows else 0)          # (off by default: measured slower on the MI355X; kept correct)
         eng.set_option('head_band', band)
         eng.load_state_dict(sd)
         eng.plan(2)
@@ -913,12 +881,12 @@ def test_emulated_sparse_pool_stores_leave_the_same_map(sdt):
 # every option's default, read off the members' initialisers in engine.h before the options became one table: the record that no default moved
 OPTION_DEFAULTS = {
     'full_taps': 0, 'streams': 1, 'graph': 0, 'fused_mlp': 1, 'mlp_split': -1, 'row_conv': 1, 'fused_rc': 1, 'dw_tile': 1, 'stem_mfma': 1, 'point_stream2': -1,
-    'head_batch': 1, 'head_fuse': 1, 'head_fuse_dbg': 0, 'side_priority': 3, 'head_lds_pad': 0, 'head_stream': 0, 'split_decoders': 0, 'group_wpc': 4096,
+    'head_batch': 1, 'head_fuse': 1, 'side_priority': 3, 'head_stream': 0, 'split_decoders': 0, 'group_wpc': 4096,
     'group_max': 1024, 'dec_fork': 1, 'radar_start': -2, 'pipeline': 0, 'pool_strip': 2, 'fused_mv2': 1, 'dw_even': 1, 'xca_mfma': 1, 'xca_frame': 0,
     'xca_fold_mfma': 1, 'xca_slice': 0, 'xca_front_waves': 0, 'xca_back_waves': 0, 'gemm_rows': 1, 'radar_rows4': 2, 'radar_skip': 1, 'radar_bg': 1,
-    'radar_pool_sparse': 1, 'radar_compact': 1, 'head_mfma': 0, 'head_rows': 2, 'xwait2_op': -1, 'gemm_blocks': 0, 'sdta_fuse': 1, 'level_chain': 1,
-    'level_rows': 0, 'mlp_band': 1, 'mlp_band_run': 0, 'mlp_band_dbg': 0, 'mlp_band_lean': 0, 'head_band': 40, 'head_grid': 0, 'head_debug': 0, 'attn_mfma': 1,
-    'ds_fuse': 1, 'sa_fuse': 0, 'pn2_fps_all': 1, 'ghost_rb': 5, 'pc_chain': 1, 'mlp_split_hw': 1024, 'radar_direct': 1, 'mv_stem': 1, 'csp_fuse': 2,
+    'radar_pool_sparse': 1, 'radar_compact': 1, 'head_rows': 2, 'xwait2_op': -1, 'gemm_blocks': 0, 'sdta_fuse': 1, 'level_chain': 1,
+    'mlp_band': 1, 'head_band': 40, 'attn_mfma': 1,
+    'ds_fuse': 1, 'pn2_fps_all': 1, 'ghost_rb': 5, 'pc_chain': 1, 'mlp_split_hw': 1024, 'radar_direct': 1, 'mv_stem': 1, 'csp_fuse': 2,
     'band_rows_s3': 0, 'spp_split': 0, 'ffn_rows2': 1, 'csp_band': 40, 'ghost_fuse': 1, 'io_bf16': 0}
 
 
@@ -936,10 +904,10 @@ def _option_keys():
 
 
 def test_option_table_and_header_agree():
-    """ach_option_key enumerates the table: 67 distinct keys, each documented (in double quotes) in the ach_set_option comment of include/achelous.h; a key
-    outside the table is refused by name."""
+    """ach_option_key enumerates the table: 57 distinct keys, each documented (in double quotes) in the ach_set_option comment of include/achelous.h; a key
+    outside the table is refused by name, and so is each of the ten keys retired with their kernels (profiles/options_retired.md)."""
     keys = _option_keys()
-    assert len(keys) == 67 and len(set(keys)) == 67, keys
+    assert len(keys) == 57 and len(set(keys)) == 57, keys
     header = open(os.path.join(os.path.dirname(GOLDEN_DIR), '..', 'include', 'achelous.h')).read()
     comment = header[header.index('/* Options, set before ach_plan'):header.index('int ach_set_option(')]
     assert [k for k in keys if f'"{k}"' not in comment] == []
@@ -950,6 +918,11 @@ def test_option_table_and_header_agree():
     assert eng.L.ach_set_option(eng.h, None, 1) == -1 and eng.L.ach_last_error(eng.h) == b'null option'
     with pytest.raises(ValueError, match='unknown option: no_such_option'):
         eng.get_option('no_such_option')
+    for key in ('head_debug', 'mlp_band_dbg', 'head_fuse_dbg', 'mlp_band_run', 'mlp_band_lean', 'head_mfma', 'head_grid', 'level_rows', 'sa_fuse', 'head_lds_pad'):
+        assert eng.L.ach_set_option(eng.h, key.encode(), 1) == -1
+        assert key.encode() in eng.L.ach_last_error(eng.h)
+        with pytest.raises(ValueError, match='unknown option: ' + key):
+            eng.get_option(key)
 
 
 def test_option_defaults_are_unchanged():
@@ -976,7 +949,7 @@ def test_option_rules_are_unchanged():
     def stored(key, value):
         eng.set_option(key, value)
         return eng.get_option(key)
-    for key, value, want in (('head_lds_pad', -5, 0), ('head_lds_pad', 70000, 65536), ('head_lds_pad', 4096, 4096), ('group_wpc', -1, 0), ('group_max', -1, 0),
+    for key, value, want in (('group_wpc', -1, 0), ('group_max', -1, 0),
                              ('group_max', 256, 256), ('dec_fork', -1, 0), ('dec_fork', 9, 3), ('dec_fork', 2, 2), ('csp_fuse', -1, 0), ('csp_fuse', 5, 2),
                              ('gemm_rows', 3, 1), ('gemm_rows', 2, 2), ('gemm_rows', 4, 4), ('gemm_rows', 0, 1), ('head_band', 0, 40), ('head_band', -3, 40),
                              ('head_band', 16, 16), ('csp_band', 0, 40), ('csp_band', 8, 8), ('ghost_rb', 0, 5), ('ghost_rb', 3, 3), ('radar_skip', 7, 1),

@@ -706,7 +706,7 @@ def test_forward_detect_equals_the_three_calls():
                 assert int(cnt.max()) > 0
 
 
-@pytest.mark.parametrize('option', ['fused_mlp', 'row_conv', 'fused_rc', 'dw_tile', 'head_batch', 'split_decoders', 'head_stream', 'stem_mfma', 'radar_start', 'head_mfma', 'radar_skip', 'dw_even', 'radar_rows4', 'xca_mfma', 'head_rows', 'head_fuse', 'mlp_band', 'ghost_fuse', 'ds_fuse'])
+@pytest.mark.parametrize('option', ['fused_mlp', 'row_conv', 'fused_rc', 'dw_tile', 'head_batch', 'split_decoders', 'head_stream', 'stem_mfma', 'radar_start', 'radar_skip', 'dw_even', 'radar_rows4', 'xca_mfma', 'head_rows', 'head_fuse', 'mlp_band', 'ghost_fuse', 'ds_fuse'])
 def test_fused_kernels_agree_with_the_layerwise_path(option):
     """Every fused / batched kernel has a switch back to the layer-wise launches it replaced (include/achelous.h): the two plans
     must agree — to fp32 rounding in the fp32 engine (different summation order), and within the bf16 tolerance in the bf16
@@ -731,35 +731,6 @@ def test_fused_kernels_agree_with_the_layerwise_path(option):
             # (twice the bound each plan is held to against the truth — H16_TOL — not round 3's 2 x bf16_bound >= 4e-2)
             tol = 1e-4 if dt == torch.float32 else 2.0 * H16_TOL[k]
             assert _rel(a.float(), b.float()) <= tol, (option, dt, k, _rel(a.float(), b.float()), tol)
-
-
-@pytest.mark.parametrize('res,batch', [(320, 3), (416, 1), (96, 2)])
-def test_mfma_bilinear_head_matches_the_gather_head(res, batch):
-    """bf16 engine: the fused last decoder level with its bilinear phase on the matrix cores (channel-planar t, interpolation weights split
-    hi + lo: exact to 2^-17; option head_mfma = 1, off by default: measured slower) against the per-position gather kernel.  Both end in the same fp32 tail, so the two
-    segmentation outputs may differ by isolated bf16 rounding flips only.  416 and 96 have ragged 12 x 16 tiles at the right / bottom
-    edges; the last frame's last row exercises the window load that starts in the tensor's final 16 bytes."""
-    g = Golden('en_s0')
-    kw = dict(ctor_kwargs(g.meta), resolution=res)
-    m = Achelous(**kw).eval()
-    m.load_state_dict(g.calibrate(condition_state_dict(m.state_dict(), seed=g.meta['weight_seed'])), strict=True)
-    m = m.cuda()
-    x, xr, xp = make_inputs(batch, 23, resolution=res, pc_channels=kw['pc_channels'])
-    xs, rs, ps = x.cuda().bfloat16(), xr.cuda().bfloat16(), xp.cuda().bfloat16()
-    m.engine_options = {'head_rows': 0}          # the gather (LDS tile) head: both kernels of this test keep [x1 | x2] in fp32 through the head's 1x1
-    with torch.no_grad():
-        old = m(xs, rs, ps)
-        e = _engine_of(m, torch.bfloat16)
-        e.set_option('head_mfma', 1)
-        e.plan(batch)
-        new = m(xs, rs, ps)
-        torch.cuda.synchronize()
-        e.set_option('head_mfma', 0)
-        e.plan(batch)
-    for k, a, b in (('se_seg', new[1], old[1]), ('lane_seg', new[2], old[2])):
-        a, b = a.float(), b.float()
-        assert _rel(a, b) <= 1.6e-2, (k, _rel(a, b))                      # one bf16 ulp of the largest value
-        assert float((a != b).float().mean()) < 5e-3, (k, float((a != b).float().mean()))
 
 
 @pytest.mark.parametrize('cells', [0, 8, 256, -1])
@@ -1165,55 +1136,6 @@ def test_xca_launch_forms_against_the_reference_fixture(name):
         for k in H16_TOL:
             assert _rel(res[key][k].float(), res['four'][k].float()) < H16_TOL[k], (key, k)
         assert torch.equal(res[key]['pc_seg'], res['four']['pc_seg'])
-
-
-@pytest.mark.parametrize('name,blocks', [('en_s0', 5), ('en_s2', 8)])
-def test_persistent_band_run_is_bit_identical_to_the_separate_launches(name, blocks):
-    """Stage 2's ConvEncoder blocks as ONE persistent launch with per-frame barriers between the blocks (k_mlpband.h mlp_band_run_kernel, option mlp_band_run = 1; off by
-    default: measured no faster) against one launch per block (mlp_band_run = 0): the same kernel body on the same data — every output and every backbone tap bit-identical, over repeated
-    forwards (the barrier counters are monotonic across launches), plain and pipelined, both 16-bit storages, with the side streams busy beside it."""
-    g = Golden(name)
-    kw = ctor_kwargs(g.meta)
-    for storage in ('f16', 'bf16'):
-        batches = []
-        for i in range(3):
-            x, xr, xp = make_inputs(16, 800 + i, resolution=kw['resolution'], pc_channels=kw['pc_channels'], dense_radar=(i == 1))
-            batches.append(tuple(t.cuda().bfloat16() for t in (x, xr, xp)))
-        res = {}
-        for run in (1, 0):
-            m, _ = _model(g)
-            m.bf16_storage = storage
-            m.engine_options = {'mlp_band_run': run}
-            outs = []
-            with torch.no_grad():
-                for rep in range(4):
-                    for b in batches:
-                        outs.append([t.clone() for t in (lambda r: (*r[0][0], r[0][1], r[0][2], r[0][3], *r[1]))(m.forward_detect(*b, 0.05, 0.5, 100))])
-                torch.cuda.synchronize()
-                names = [o['op'] for o in _engine_of(m, torch.bfloat16).op_table_full()]
-                taps = {t: _engine_of(m, torch.bfloat16).read_tap(t) for t in _engine_of(m, torch.bfloat16).tap_names() if t.startswith('backbone.s2')}
-                prev, pip = None, []
-                for rep in range(3):
-                    for b in batches:
-                        nxt = m.submit_detect(*b, 0.05, 0.5, 100)
-                        if prev is not None:
-                            r = prev.wait()
-                            pip.append([t.clone() for t in (*r[0][0], r[0][1], r[0][2], r[0][3], *r[1])])
-                        prev = nxt
-                r = prev.wait()
-                pip.append([t.clone() for t in (*r[0][0], r[0][1], r[0][2], r[0][3], *r[1])])
-                torch.cuda.synchronize()
-            res[run] = (outs, taps, pip, names)
-        merged = [n for n in res[1][3] if '..+' in n]
-        assert len(merged) == 1 and merged[0].endswith(f'..+{blocks - 1}') and len(res[0][3]) - len(res[1][3]) == blocks - 1, (merged, len(res[0][3]), len(res[1][3]))
-        for a, b_ in zip(res[1][0], res[0][0]):
-            for p, q in zip(a, b_):
-                assert torch.equal(p, q), storage
-        for t in res[1][1]:
-            assert torch.equal(res[1][1][t], res[0][1][t]), (storage, t)
-        for k, a in enumerate(res[1][2]):
-            for p, q in zip(a, res[1][0][k % 3]):
-                assert torch.equal(p, q), (storage, 'pipelined', k)
 
 
 def test_packed_fp16_deformable_blend_stays_within_a_few_fp16_ulps_of_the_fp32_blend():
