@@ -22,6 +22,7 @@
 #include "k_mvit.h"
 #include "k_nhwc.h"
 #include "k_points.h"
+#include "k_poolformer.h"
 #include "k_pn2.h"
 #include "k_prepost.h"
 #include "k_radar.h"
@@ -1015,6 +1016,108 @@ public:
         x = mv2block(pfx + ".mv2.6", x, 2, mc.ch[8]);
         x = mvit_block(pfx + ".mvit.2", x, 3);
         feats[3] = mv_conv(pfx + ".conv2", x, 1, 1);
+    }
+
+    // ------------------------------------------------------------------------------------------ PoolFormer (k_poolformer.h)
+    struct Mom { float* p = nullptr; int P = 0; };          // per-sample partial moments of a tensor: [B][P][4] fp32 (count, mean, M2, -)
+    Mom alloc_mom(int B, int P) { Mom m; m.P = P; m.p = alloc_f32(size_t(B) * P * 4); return m; }
+    // `dst[i]` (optional, may be null): where the fork norm of stage i writes its map
+    void poolformer(const std::string& pfx, A feats[4], const A* const dst[4]) {                 // poolformer.py forward_tokens (fork_feat)
+        static const int kDepths[3][4] = {{2, 2, 6, 2}, {4, 4, 12, 4}, {6, 6, 18, 6}};
+        const int* dep = kDepths[cfg.phi == ACH_PHI_S0 ? 0 : (cfg.phi == ACH_PHI_S1 ? 1 : 2)];
+        const int* wd = widths();
+        const int B = batch, R = cfg.resolution;
+        const float eps = 1e-5f;
+        A x;
+        Mom mx;
+        {   // patch_embed: conv 7x7 / 4 / pad 2 + bias from the NCHW image; K ordered (dy, c, dx padded to 8) — pf_stem_kernel
+            const HostTensor& w = W(pfx + ".patch_embed.proj.weight");
+            if (w.shape.size() != 4 || w.shape[0] != 32 || w.shape[1] != 3 || w.shape[2] != 7 || w.shape[3] != 7 || wd[0] != 32) throw AchError{ACH_ERR_UNSUPPORTED, "PoolFormer stem shape"};
+            Lin ls; ls.N = 32; ls.K = PF_STEM_K; ls.w.assign(size_t(32) * PF_STEM_K, 0.f); ls.b = W(pfx + ".patch_embed.proj.bias").data;
+            for (int o = 0; o < 32; ++o)
+                for (int c = 0; c < 3; ++c)
+                    for (int dy = 0; dy < 7; ++dy)
+                        for (int dx = 0; dx < 7; ++dx) ls.w[size_t(o) * PF_STEM_K + pf_stem_k(c, dy, dx)] = w.data[((size_t(o) * 3 + c) * 7 + dy) * 7 + dx];
+            const Packed pk = pack(ls);
+            if (pk.NT != 2 || pk.nchunks != 1) throw AchError{ACH_ERR_INVALID, "PoolFormer stem packing"};
+            const int Ho = R / 4, segs = cdiv(Ho, PF_STEM_SEG);
+            x = alloc(B, Ho, Ho, 32);
+            mx = alloc_mom(B, Ho * segs);
+            PfStemParams sp{nullptr, x.p, x.ld, pk.w, pk.b, mx.p, R, R, Ho, Ho, segs};
+            const dim3 grid(unsigned(Ho * segs), unsigned(B)), block(256);
+            const void** img = &io.image;
+            const bool alt = io_alt();
+            add_op(pfx + ".patch_embed", [sp, grid, block, img, alt](hipStream_t s) mutable { sp.X = *img; if (alt) ACH_LAUNCH((pf_stem_kernel<T, IOB>), grid, block, s, sp); else ACH_LAUNCH((pf_stem_kernel<T, T>), grid, block, s, sp); },
+                   (double(B) * 3 * R * R + double(x.rows()) * 32) * sizeof(T), 2.0 * double(x.rows()) * 147 * 32);
+            tap("backbone.stem", x);
+        }
+        for (int i = 0; i < 4; ++i) {
+            if (i > 0) {    // down-sampling conv 3x3 / 2 / pad 1 + bias on the un-normalised stage output: the implicit GEMM, then one moments pass
+                const std::string d = pfx + ".network." + std::to_string(2 * i - 1) + ".proj";
+                Lin l = conv_lin(d + ".weight", d + ".bias", x.C, int(x.ld), 3);
+                if (l.N != wd[i]) throw AchError{ACH_ERR_MISSING_KEY, "PoolFormer down-sampling width at " + d};
+                x = conv_gemm(d, x, l, 3, 2, ACT_NONE);
+                tap("backbone.ds" + std::to_string(i), x);
+                const int HW = x.H * x.W;
+                mx = alloc_mom(B, cdiv(HW, PF_MOM_PIX));
+                PfMomParams mp{x.p, x.ld, mx.p, HW, x.C};
+                const dim3 grid(unsigned(mx.P), unsigned(B)), block(256);
+                add_op(d + ".moments", [mp, grid, block](hipStream_t s) { ACH_LAUNCH(pf_moments_kernel<T>, grid, block, s, mp); }, double(x.rows()) * x.C * sizeof(T));
+            }
+            const int C = x.C, HW = x.H * x.W;
+            if (C != wd[i] || C % 8 != 0 || x.ld % VEC != 0) throw AchError{ACH_ERR_UNSUPPORTED, "PoolFormer stage width"};
+            for (int j = 0; j < dep[i]; ++j) {
+                const std::string bp = pfx + ".network." + std::to_string(2 * i) + "." + std::to_string(j);
+                // token mixer: a_c = ls1_c * gamma1_c (mean and beta of norm1 cancel in pool(GN x) - GN x)
+                const auto& ls1 = W(bp + ".layer_scale_1").data; const auto& g1 = W(bp + ".norm1.weight").data;
+                if (int(ls1.size()) != C || int(g1.size()) != C) throw AchError{ACH_ERR_MISSING_KEY, "PoolFormer block widths at " + bp};
+                std::vector<float> a(static_cast<size_t>(C));
+                for (int c = 0; c < C; ++c) a[size_t(c)] = ls1[size_t(c)] * g1[size_t(c)];
+                A y = alloc(B, x.H, x.W, C);
+                const int RB = pf_mixer_band(x.H);
+                Mom my = alloc_mom(B, cdiv(x.H, RB));
+                {
+                    PfMixParams mp{x.p, x.ld, y.p, y.ld, up_f32(a), mx.p, mx.P, my.p, x.H, x.W, C, RB, eps};
+                    const dim3 grid(unsigned(my.P), unsigned(B)), block(256);
+                    add_op(bp + ".mixer", [mp, grid, block](hipStream_t s) { ACH_LAUNCH(pf_mixer_kernel<T>, grid, block, s, mp); }, 2.0 * double(x.rows()) * C * sizeof(T));
+                }
+                // MLP: gamma2 -> W1, W1 beta2 -> b1, ls2 -> W2 / b2; (mu, rstd) per sample from y's partial moments
+                Lin l1 = lin(bp + ".mlp.fc1.weight", bp + ".mlp.fc1.bias");
+                fold_ln_in(l1, bp + ".norm2");
+                Lin l2 = lin(bp + ".mlp.fc2.weight", bp + ".mlp.fc2.bias");
+                fold_scale_out(l2, W(bp + ".layer_scale_2").data);
+                const int DT = mlp_pick_dt(C);
+                if (DT == 0 || DT > 18 || l1.K != C || l2.N != C || l2.K != l1.N) throw AchError{ACH_ERR_UNSUPPORTED, "PoolFormer MLP shapes at " + bp};
+                A z = alloc(B, x.H, x.W, C);
+                PfMlpParams q;
+                std::memset(&q, 0, sizeof(q));
+                chain_weights(q.m, C, DT, l1, ACT_GELU, l2);
+                q.m.X = y.p; q.m.ldx = y.ld; q.m.Y = z.p; q.m.ldy = z.ld; q.m.M = y.rows();
+                // per-sample map size, not batch, decides the geometry (as for mlp_kernel): four waves per tile on the small maps
+                const bool split = mlp_split < 0 ? HW <= mlp_split_hw : mlp_split != 0;
+                Mom mz = alloc_mom(B, pf_mlp_blocks(HW, split));
+                q.min = my.p; q.Pin = my.P; q.mout = mz.p; q.HW = HW; q.eps = eps; q.tpw = pf_mlp_tpw(HW, split);
+                add_op(bp + ".mlp", [q, DT, split, B](hipStream_t s) { launch_pf_mlp<T>(q, DT, split, B, s); },
+                       2.0 * double(y.rows()) * C * sizeof(T), 4.0 * double(y.rows()) * C * l1.N);
+                tap("backbone.s" + std::to_string(i) + ".b" + std::to_string(j), z);
+                x = z; mx = mz;
+            }
+            // fork norm (norm0 / norm2 / norm4 / norm6): the map the neck reads
+            const std::string n = pfx + ".norm" + std::to_string(2 * i);
+            const auto& gw = W(n + ".weight").data; const auto& gb = W(n + ".bias").data;
+            if (int(gw.size()) != C || int(gb.size()) != C) throw AchError{ACH_ERR_MISSING_KEY, "PoolFormer output norm width at " + n};
+            A out;
+            if (dst && dst[i]) {
+                out = *dst[i];
+                reached(kPtConcatSlice);        // (the next launch writes a slice of the neck's concat buffer)
+                if (out.B != x.B || out.H != x.H || out.W != x.W || out.C != C || out.ld % VEC != 0) throw AchError{ACH_ERR_INVALID, "PoolFormer output destination does not match the stage"};
+            } else out = alloc(B, x.H, x.W, C);
+            PfNormParams np{x.p, x.ld, out.p, out.ld, up_f32(gw), up_f32(gb), mx.p, mx.P, HW, C, eps};
+            const dim3 grid(unsigned(cdiv(HW * (C / VEC), 256)), unsigned(B)), block(256);
+            add_op(n, [np, grid, block](hipStream_t s) { ACH_LAUNCH(pf_norm_apply_kernel<T>, grid, block, s, np); }, 2.0 * double(x.rows()) * C * sizeof(T));
+            feats[i] = out;
+            if (i < 3) reached(Point(kPtStage0 + i));
+        }
     }
 
     // ------------------------------------------------------------------------------------------ neck (a7-a13)
@@ -2194,6 +2297,16 @@ public:
             const A d1 = cat_buf[0].slice(wd[1], wd[1]), d2 = cat_buf[1].slice(wd[2], wd[2]);
             const A* dst[4] = {nullptr, &d1, &d2, nullptr};
             edgenext("image_radar_encoder.fpn.backbone", m, dst);
+        }
+        else if (cfg.backbone == ACH_BACKBONE_POOLFORMER) {
+            // the same direct write: the fork norms of stages 1 / 2 are the launches that produce the neck's inputs
+            const int* wd = widths();
+            const int R = cfg.resolution;
+            cat_buf[0] = alloc(batch, R / 8, R / 8, 2 * wd[1]);
+            cat_buf[1] = alloc(batch, R / 16, R / 16, 2 * wd[2]);
+            const A d1 = cat_buf[0].slice(wd[1], wd[1]), d2 = cat_buf[1].slice(wd[2], wd[2]);
+            const A* dst[4] = {nullptr, &d1, &d2, nullptr};
+            poolformer("image_radar_encoder.fpn.backbone", m, dst);
         }
         else mobilevit("image_radar_encoder.fpn.backbone", m);
         A q[3];

@@ -100,8 +100,8 @@ def _check_supported(backbone, neck, pc_seg, phi, num_seg, image_channels, radar
     """ONE error that lists every constructor argument outside the built path — the reference's own defaults
     (`backbone='ef'`, nets/Achelous.py:27) are among them."""
     bad = []
-    if backbone not in ('en', 'mv'):
-        bad.append(f"backbone={backbone!r} (built: 'en' EdgeNeXt, 'mv' MobileViT; the reference default 'ef' and the other six backbones are out of scope)")
+    if backbone not in ('en', 'mv', 'pf'):
+        bad.append(f"backbone={backbone!r} (built: 'en' EdgeNeXt, 'mv' MobileViT, 'pf' PoolFormer; the reference default 'ef' and the other five backbones are out of scope)")
     if neck not in ('gdf', 'cdf'):
         bad.append(f"neck={neck!r} (built: 'gdf' Ghost-Dual-FPN, 'cdf' CSP-Dual-FPN)")
     if pc_seg not in ('pn', 'pn2', 'pn2_msg', 'none'):
@@ -175,6 +175,12 @@ class Achelous(nn.Module):
         st['_op_token'] = None
         return st
 
+    def train(self, mode=True):
+        # PoolFormer is built for inference only: no GroupNorm(1) backward kernels exist, and the training graph must not fall into EdgeNeXt code
+        if mode and self.__dict__.get('backbone') == 'pf':
+            raise NotImplementedError("achelous_amd.Achelous: training mode is not built for backbone='pf' (PoolFormer is inference only; 'en' and 'mv' train)")
+        return super().train(mode)
+
     def _init_like_reference(self):
         """Default values in the spirit of the reference's initialisers (not bit-identical: real use loads a checkpoint)."""
         g = torch.Generator().manual_seed(0)
@@ -183,6 +189,8 @@ class Achelous(nn.Module):
             with torch.no_grad():
                 if leaf in ('gamma', 'gamma_xca'):
                     p.fill_(1e-6)
+                elif leaf in ('layer_scale_1', 'layer_scale_2'):
+                    p.fill_(1e-5)                                   # poolformer.py layer_scale_init_value
                 elif leaf == 'temperature' or leaf in ('cbias', 'sbias'):
                     p.fill_(1.0)
                 elif leaf in ('cweight', 'sweight'):

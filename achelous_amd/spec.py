@@ -21,6 +21,7 @@ MOBILEVIT = {  # backbone/vision/mobilevit_modules/mobilevit.py:225-240
     'S1': dict(dims=[96, 120, 144], ch=[16, 32, 32, 32, 48, 48, 120, 120, 120, 120, 224], exp=4),
     'S2': dict(dims=[144, 192, 240], ch=[16, 32, 32, 32, 64, 64, 144, 144, 144, 144, 288], exp=4),
 }
+POOLFORMER = {'S0': [2, 2, 6, 2], 'S1': [4, 4, 12, 4], 'S2': [6, 6, 18, 6]}   # poolformer_modules/poolformer.py poolformer_S0/S1/S2: block depths; the widths are WIDTHS[phi]
 
 
 class _Spec(list):
@@ -230,6 +231,28 @@ def _mobilevit(s, pfx, phi):                    # mobilevit.py:168-196
     _conv_bn_seq(s, pfx + '.conv2', ch[-1], ch[-2], 1)
 
 
+def _poolformer(s, pfx, phi):                   # poolformer_modules/poolformer.py (fork_feat=True: four output norms, no classifier tail)
+    dims, depths = WIDTHS[phi], POOLFORMER[phi]
+    s.wb(pfx + '.patch_embed.proj', (dims[0], 3, 7, 7))
+    for i in range(4):
+        d = dims[i]
+        for j in range(depths[i]):
+            b = f'{pfx}.network.{2 * i}.{j}'
+            s.p(b + '.layer_scale_1', d)
+            s.p(b + '.layer_scale_2', d)
+            s.ln(b + '.norm1', d)                                   # GroupNorm(1, d)
+            s.ln(b + '.norm2', d)
+            s.wb(b + '.mlp.fc1', (4 * d, d, 1, 1))
+            s.wb(b + '.mlp.fc2', (d, 4 * d, 1, 1))
+        if i < 3:
+            s.wb(f'{pfx}.network.{2 * i + 1}.proj', (dims[i + 1], d, 3, 3))
+    for i in range(4):
+        s.ln(f'{pfx}.norm{2 * i}', dims[i])
+
+
+_BACKBONES = {'en': _edgenext, 'mv': _mobilevit, 'pf': _poolformer}
+
+
 def _ghost(s, pfx, inp, oup):                   # ghost_conv.py:6-23
     init = math.ceil(oup / 2)
     _conv_bn_seq(s, pfx + '.primary_conv', init, inp, 1)
@@ -267,10 +290,7 @@ def _csp_layer(s, pfx, cin, cout):                                  # cspdualfpn
 def _neck_csp(s, phi, backbone, num_seg):       # cspdualfpn.py:81-191
     f = 'image_radar_encoder.fpn'
     w = WIDTHS[phi]
-    if backbone == 'en':
-        _edgenext(s, f + '.backbone', phi)
-    else:
-        _mobilevit(s, f + '.backbone', phi)
+    _BACKBONES[backbone](s, f + '.backbone', phi)
     c_ = w[3] // 2
     _baseconv(s, f + '.spp.cv1', w[3], c_)
     _baseconv(s, f + '.spp.cv2', 4 * c_, w[3])
@@ -293,10 +313,7 @@ def _neck_csp(s, phi, backbone, num_seg):       # cspdualfpn.py:81-191
 def _neck(s, phi, backbone, num_seg):           # ghostdualfpn.py:42-152
     f = 'image_radar_encoder.fpn'
     w = WIDTHS[phi]
-    if backbone == 'en':
-        _edgenext(s, f + '.backbone', phi)
-    else:
-        _mobilevit(s, f + '.backbone', phi)
+    _BACKBONES[backbone](s, f + '.backbone', phi)
     c_ = w[3] // 2
     _baseconv(s, f + '.spp.cv1', w[3], c_)
     _baseconv(s, f + '.spp.cv2', 4 * c_, w[3])
@@ -379,8 +396,8 @@ def state_dict_spec(num_det, num_seg, phi='S0', backbone='en', pc_channels=6, pc
     `pc_seg_model.*` keys are those of our own PointNet++ specification (PN2 above)."""
     if pc_seg not in ('pn', 'pn2', 'pn2_msg', 'none'):
         raise NotImplementedError(f"pc_seg={pc_seg!r}: 'pn' (reference), 'pn2' / 'pn2_msg' (own specifications) and 'none' (Achelous3T, nets/Achelous.py:56-76) are built")
-    if phi not in WIDTHS or backbone not in ('en', 'mv') or neck not in ('gdf', 'cdf'):
-        raise NotImplementedError(f"backbone={backbone!r}, phi={phi!r}, neck={neck!r}: only 'en'/'mv' with S0/S1/S2 and gdf/cdf are built")
+    if phi not in WIDTHS or backbone not in _BACKBONES or neck not in ('gdf', 'cdf'):
+        raise NotImplementedError(f"backbone={backbone!r}, phi={phi!r}, neck={neck!r}: only 'en'/'mv'/'pf' with S0/S1/S2 and gdf/cdf are built")
     s = _Spec()
     if pc_seg != 'none':
         if pc_seg == 'pn':

@@ -52,8 +52,8 @@ def condition_state_dict(sd, seed=0):
             v = N(0.1)
         elif leaf == 'running_var':
             v = U(0.5, 1.5)
-        elif leaf in ('gamma', 'gamma_xca'):
-            v = U(0.2, 0.6)
+        elif leaf in ('gamma', 'gamma_xca', 'layer_scale_1', 'layer_scale_2'):
+            v = U(0.2, 0.6)                      # layer scales: large enough that an error inside the scaled branch is not attenuated away
         elif leaf == 'temperature':
             v = U(0.5, 2.0)
         elif leaf in ('cweight', 'sweight'):

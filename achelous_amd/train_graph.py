@@ -40,6 +40,8 @@ _POS_TABLES = {}        # (H, W, device, hidden, temperature) -> the Fourier pos
 
 class TrainGraph:
     def __init__(self, model):
+        if model.backbone not in ('en', 'mv'):
+            raise NotImplementedError(f"training mode is not built for backbone={model.backbone!r} (inference only; 'en' and 'mv' train)")
         self.m = model
         self.p = dict(model.named_parameters())
         self.b = dict(model.named_buffers())
