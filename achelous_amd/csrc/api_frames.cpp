@@ -1,5 +1,5 @@
 // api_frames.cpp — the entries that work on ragged batches of frames: the resample pass, training batches and radar inputs assembled on the device (k_data.h,
-// k_radarmap.h), serving at every frame's own size (k_serve.h), drawing (k_draw.h) and the heat-map mode (k_heatmap.h).  What they share is the host-side check of a frame table against its arenas
+// k_radarmap.h), serving at every frame's own size (k_serve.h), drawing (k_draw.h), the heat-map mode (k_heatmap.h) and the point-class scatter (k_scatter.h).  What they share is the host-side check of a frame table against its arenas
 // BEFORE anything is launched: a bad table must never become an out-of-bounds access on the device.  See api.cpp / api_util.h.
 #include <algorithm>
 #include <cmath>
@@ -12,7 +12,9 @@
 #include "k_serve.h"
 #include "k_draw.h"
 #include "k_heatmap.h"
+#include "k_scatter.h"
 #include "../../include/achelous_heatmap.h"
+#include "../../include/achelous_points.h"
 
 static const int64_t SIZE_TOP = (1L << 30) - 1;      // a frame's H and W (the drawing entry has a limit of its own)
 static_assert(int(ach::DATA_F32) == KIND_F32 && int(ach::DATA_BF16) == KIND_BF16 && int(ach::DATA_F16) == KIND_F16 && int(ach::DATA_U8_HWC) == KIND_U8, "the data entries' kinds are ElemKind");
@@ -302,6 +304,52 @@ int ach_heatmap_frames(int32_t det_kind, int32_t R, int32_t num_det, int32_t bat
         ach::HeatParams p{scores, stats, base, reinterpret_cast<const long long*>(table_dev), cmap_dev, mask, out, R, A, alpha};
         ACH_LAUNCH(ach::heat_mask_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
         if (colour) ACH_LAUNCH(ach::heat_colour_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
+    });
+}
+
+// ---- the picture of the radar point classes on served frames (k_scatter.h): the unique sorted (u, v, s, class) rows of every frame and their discs painted in place, in
+// two launches.  Stateless.  The host copy of the frame table is checked against the arena and the cloud buffer before anything is launched; what comes from DEVICE
+// data (indices, class ids, u, v, s) is bounded by the kernels themselves.
+int ach_scatter_points_frames(uint8_t* arena, int64_t arena_bytes, const int64_t* table_host, const int64_t* table_dev, int32_t batch, const void* clouds,
+                              int64_t cloud_elems, int32_t cloud_kind, const int64_t* indices_dev, const int64_t* point_class, int32_t num_points,
+                              int32_t num_classes, const uint8_t* colours_dev, int32_t colour_mode, int32_t range_lo, int32_t range_hi, float alpha, double k,
+                              int32_t max_radius, double* rows, int32_t* count, int32_t* class_range, double* discs, int64_t discs_bytes, int32_t* boxes,
+                              int64_t boxes_bytes, void* stream) {
+    return stateless(stream, [&](hipStream_t s) {
+        need(arena && table_host && table_dev && clouds && point_class && colours_dev && rows && count && class_range && discs && boxes && batch > 0 && batch <= 65535 &&
+             arena_bytes > 0 && cloud_elems >= 0 && (cloud_kind == ach::SCATTER_IN_F32 || cloud_kind == ach::SCATTER_IN_F64), "ach_scatter_points_frames");
+        need(num_points >= 1, "ach_scatter_points_frames: num_points is 1..4096");
+        if (num_points > ach::SCATTER_MAX_POINTS) throw ach::AchError{ACH_ERR_UNSUPPORTED, "ach_scatter_points_frames: more than 4096 points per frame"};
+        need(num_classes >= 1 && num_classes <= ach::SCATTER_MAX_CLASSES, "ach_scatter_points_frames: num_classes is 1..256");
+        need(colour_mode >= ach::SCATTER_CMAP_AUTO && colour_mode <= ach::SCATTER_PALETTE, "ach_scatter_points_frames: colour_mode is 0 (colour map), 1 (fixed range) or 2 (palette)");
+        if (colour_mode == ach::SCATTER_CMAP_FIXED) need(range_lo >= 0 && range_lo <= range_hi && range_hi <= 255, "ach_scatter_points_frames: a fixed class range has 0 <= lo <= hi <= 255");
+        need(alpha >= 0.f && alpha <= 1.f, "ach_scatter_points_frames: alpha lies in [0, 1]");
+        need(max_radius >= 1 && max_radius <= ach::SCATTER_MAX_RADIUS, "ach_scatter_points_frames: max_radius is 1..256");
+        need(std::isfinite(k) && k > 0.0, "ach_scatter_points_frames: k = size_scale^2 / 4 is finite and above 0");
+        need((reinterpret_cast<uintptr_t>(arena) & 3u) == 0 && (reinterpret_cast<uintptr_t>(clouds) & (cloud_kind == ach::SCATTER_IN_F64 ? 7u : 3u)) == 0 &&
+             ((reinterpret_cast<uintptr_t>(indices_dev) | reinterpret_cast<uintptr_t>(point_class) | reinterpret_cast<uintptr_t>(rows)) & 7u) == 0 &&
+             ((reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(class_range)) & 3u) == 0,
+             "ach_scatter_points_frames: the arena is 4-byte aligned, clouds, indices, classes and rows to their element size");
+        const int64_t samples = int64_t(batch) * num_points;
+        need(aligned16(discs, boxes) && discs_bytes >= samples * 32 && boxes_bytes >= samples * 16,
+             "ach_scatter_points_frames: the workspaces are 16-byte aligned and hold 32 and 16 bytes per sample");
+        long blocks = 0;
+        for (int b = 0; b < batch; ++b) {
+            const int64_t* f = table_host + long(b) * ach::SCATTER_TABLE_COLS;
+            const int64_t off = f[0], H = f[1], W = f[2], pitch = f[3], coff = f[4], n = f[5], F = f[6], stride = f[7];
+            need(dims_ok(H, W, 1L << 20), "ach_scatter_points_frames: a frame's H and W are 1..2^20");
+            need(frame_fits(off, H, 3 * W, pitch, pitch, arena_bytes, 4), "ach_scatter_points_frames: a frame's extent passes the arena (offset and pitch are multiples of 4, pitch >= 3 W)");
+            need(n >= 0 && n < (1L << 40) && F >= 1 && F < (1L << 20) && frame_fits(coff, n, F, stride, F, cloud_elems, 1, 1L << 20),
+                 "ach_scatter_points_frames: a cloud's extent passes the cloud buffer");
+            for (int c = 8; c < 11; ++c) need(f[c] >= 0 && f[c] < F, "ach_scatter_points_frames: a column index is not below F");
+            blocks = std::max(blocks, ach::cdivl(W, ach::SCATTER_TW) * ach::cdivl(H, ach::SCATTER_TH));
+        }
+        need(blocks < (1L << 31), "ach_scatter_points_frames: a frame is too large");
+        ach::ScatterParams p{clouds, reinterpret_cast<const long long*>(table_dev), reinterpret_cast<const long long*>(indices_dev), reinterpret_cast<const long long*>(point_class),
+                             colours_dev, arena, rows, count, class_range, discs, boxes, k, double(max_radius) * double(max_radius), num_points,
+                             ach::scatter_pow2(num_points), num_classes, cloud_kind, colour_mode, range_lo, range_hi, alpha};
+        ACH_LAUNCH(ach::scatter_rows_kernel, dim3(unsigned(batch)), dim3(256), s, p);
+        ACH_LAUNCH(ach::scatter_tiles_kernel, dim3(unsigned(blocks), unsigned(batch)), dim3(256), s, p);
     });
 }
 

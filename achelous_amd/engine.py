@@ -74,10 +74,14 @@ for _name in EXTENSION_HEADERS:
     with open(os.path.join(os.path.dirname(HEADER), _name)) as _f:
         EXTENSIONS.update(parse_header(_f.read()))
 
+# include/achelous_points.h (the point-class scatter on served frames): a table of its own, read and bound the same way
+with open(os.path.join(os.path.dirname(HEADER), 'achelous_points.h')) as _f:
+    POINT_ENTRIES = parse_header(_f.read())
+
 
 class NativeLibrary:
-    """dlopen + prototypes for every symbol declared in include/achelous.h (SYMBOLS) and in its extension headers (EXTENSIONS), derived from the headers themselves
-    (parse_header)."""
+    """dlopen + prototypes for every symbol declared in include/achelous.h (SYMBOLS), in its extension headers (EXTENSIONS) and in include/achelous_points.h
+    (POINT_ENTRIES), derived from the headers themselves (parse_header)."""
     SYMBOLS = tuple(PROTOTYPES)
 
     def __init__(self, path):
@@ -88,7 +92,7 @@ class NativeLibrary:
         self.lib = ctypes.CDLL(path)
         # (an entry is bound where the library exports it: the co-residency tests also load libraries built from older sources; tests/test_abi_and_host.py
         #  holds the product to every declared symbol, and calling an entry a library lacks raises AttributeError)
-        for name, (restype, argtypes) in {**PROTOTYPES, **EXTENSIONS}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **EXTENSIONS, **POINT_ENTRIES}.items():
             fn = getattr(self.lib, name, None)
             if fn is not None:
                 fn.restype, fn.argtypes = restype, argtypes

@@ -11,6 +11,7 @@
     detect_frames_from_clouds(net, frames, clouds)   + radar_feature_map_generate.ipynb   the same from raw radar point clouds (data.radar_maps_batch / radar_points_batch)
     draw_detections_frames(arena, layout, boxes, ..) achelous.py:363-433    box rings, label plates and label text drawn in place on every frame, PIL's bytes (csrc/k_draw.h)
     heatmap_frames(det, shapes, base, layout, style) achelous.py:451-555    the heat-map mode: score mask at every frame's size, its range, the jet blend (csrc/k_heatmap.h)
+    scatter_points_frames(arena, layout, shapes, ..) achelous.py:261-271    the radar point classes: unique (u, v, rcs, class) rows and their discs painted in place (csrc/k_scatter.h)
 HIP kernels through the C ABI; no CPU fallback.
 """
 import contextlib
@@ -497,7 +498,7 @@ def draw_detections_frames(arena, layout, boxes, count, shapes, style, input_sha
     them, `shapes` one (H, W) per frame, `style` a `DrawStyle`, `input_shape` the network's (R, R).  class_counts: optional int32 [B, num_classes] tensor that receives
     the number of kept rows per class id (the reference's count=True tally; skipped classes count, rows past count[b] do not).
     Two launches whatever B is; the per-frame table travels in one non-blocking copy; no host read, no synchronisation.  Returns the per-frame [H, W, 3] views.
-    Not covered: crop=True (data-dependent output sizes), the matplotlib scatter of the point classes, file output."""
+    Not covered: crop=True (data-dependent output sizes), file output (the scatter of the point classes is `scatter_points_frames`)."""
     from . import data as _data
     lib = _pass_lib(arena)
     if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
@@ -648,8 +649,145 @@ def heatmap_frames(det, shapes, base, layout=None, style=None, input_shape=None,
     return res
 
 
+# ------------------------------------------------------------------------------------------------- the point classes on the frames (csrc/k_scatter.h)
+SCATTER_TABLE_COLS, SCATTER_MAX_POINTS = 16, 4096        # k_scatter.h
+
+
+class ScatterStyle:
+    """How `scatter_points_frames` paints: `cmap` uint8 [256, 3] (None: matplotlib's default viridis, shipped as `colormaps.VIRIDIS`), normalised per frame to the
+    smallest and largest class among the frame's rows as matplotlib's `c=` does; `class_range` = (lo, hi) fixes that range for every frame, so that a class keeps its
+    colour from frame to frame (ids outside it clamp to its ends); `colors` uint8 [num_classes, 3] replaces the map by a per-class palette.  `alpha` of a disc over what
+    lies under it (the reference's 0.98).  A row's disc has the diameter size_scale * sqrt(s) pixels, its radius at most `max_radius` (1..256) pixels.  `columns`: the
+    cloud's columns of (rcs, u, v) — None: `data.MAP_COLUMNS[2:5]`, or the serving call's `columns`."""
+
+    def __init__(self, cmap=None, colors=None, class_range=None, alpha=0.98, size_scale=1.0, max_radius=64, columns=None):
+        from .colormaps import VIRIDIS
+        self.alpha, self.size_scale, self.max_radius = float(alpha), float(size_scale), int(max_radius)
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError("ScatterStyle: alpha lies in [0, 1]")
+        if not 1 <= self.max_radius <= 256 or self.max_radius != max_radius:
+            raise ValueError("ScatterStyle: max_radius is an integer in 1..256")
+        self.k = self.size_scale * self.size_scale / 4.0
+        if not (self.size_scale > 0 and math.isfinite(self.k) and self.k > 0):
+            raise ValueError("ScatterStyle: size_scale is above 0")
+        c = VIRIDIS if cmap is None else np.asarray(cmap)
+        if c.dtype != np.uint8 or c.shape != (256, 3):
+            raise ValueError("ScatterStyle: `cmap` is a uint8 [256, 3] table")
+        self.cmap = np.ascontiguousarray(c)
+        self.colors = None
+        if colors is not None:
+            p = np.asarray(colors)
+            if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 3 or not 1 <= p.shape[0] <= 256:
+                raise ValueError("ScatterStyle: `colors` is a uint8 [num_classes, 3] palette of at most 256 classes")
+            self.colors = np.ascontiguousarray(p)
+        self.class_range = None
+        if class_range is not None:
+            lo, hi = (int(v) for v in class_range)
+            if not 0 <= lo <= hi <= 255:
+                raise ValueError("ScatterStyle: class_range = (lo, hi) with 0 <= lo <= hi <= 255")
+            self.class_range = (lo, hi)
+        self.columns = None if columns is None else tuple(int(c) for c in columns)
+        if self.columns is not None and len(self.columns) != 3:
+            raise ValueError("ScatterStyle: `columns` are the cloud's three columns of rcs, u, v")
+
+    def table(self, num_classes):
+        """(the 768 colour bytes, colour mode of k_scatter.h, lo, hi)"""
+        if self.colors is not None:
+            if len(self.colors) < num_classes:
+                raise ValueError(f"ScatterStyle: `colors` holds {len(self.colors)} colours for {num_classes} classes")
+            t = np.zeros((256, 3), np.uint8)
+            t[:len(self.colors)] = self.colors
+            return t, 2, 0, 0
+        return (self.cmap, 0, 0, 0) if self.class_range is None else (self.cmap, 1, self.class_range[0], self.class_range[1])
+
+
+def scatter_points_frames(arena, layout, shapes, points, point_class, num_classes, style=None, indices=None, _columns=None):
+    """The reference's picture of the radar point classes (achelous.py:261-271) for B frames of different sizes, IN PLACE on a packed HWC uint8 arena, in two launches
+    whatever B is.  For frame b and sample j < N: (u, v, s) = the cloud's u, v and rcs columns at row indices[b, j], as float64; c = point_class[b, j].
+
+    point_rows: float64 [B, N, 4], the reference's `output_seg_pc_collections` = np.unique(concat[u, v, rcs, class], axis=0): the samples sorted ascending by
+    (u, v, s, c) by value, equal rows once, rows past point_count[b] zero.  A sample leaves when u, v or s is not finite, when its class is outside [0, num_classes)
+    (our rule: the reference would hand NaN to matplotlib) or when its index is outside its cloud.  point_count: int32 [B].
+    point_class_range: int32 [B, 2], the smallest and largest class among a frame's rows, (0, 0) without one: what matplotlib's `c=` normalises the colour map by.
+    Colour: style.cmap[0] when hi == lo, else style.cmap[min((c - lo) * 256 // (hi - lo), 255)] — byte for byte cm.viridis(Normalize(lo, hi)(c), bytes=True); or over
+    style.class_range, or style.colors[c].
+    Geometry (our rule — the reference's marker size is in points of a figure whose scale to image pixels it never fixes): a pixel has its centre at integer
+    coordinates, as imshow places it, and a row covers pixel (x, y) iff s > 0 and (x - u)^2 + (y - v)^2 <= min(size_scale^2 / 4 * s, max_radius^2), in float64, every
+    operation rounded once: a disc of diameter size_scale * sqrt(s) pixels.  No anti-aliasing: matplotlib's Agg edges are NOT reproduced, nor its figure or file output.
+    Paint: the rows in their sorted order, later over earlier, every covered pixel = Image.blend(pixel, colour, style.alpha) per covering row (PIL's arithmetic).  A
+    byte no disc covers is not written.
+
+    arena: 1-D uint8 tensor of packed HWC frames; layout: (byte offsets, pitches) per frame, or what `frames_layout(shapes)` returns (its overlay part) — multiples of 4.
+    points: a `data.Clouds`, a list of host clouds [n_i, F] (uploaded once; the columns are style.columns), or a dense device tensor [B, N, 3] = (u, v, s) float32 /
+    float64.  point_class: [B, N] integer tensor on the arena's device.  indices: [B, N] (host array or device tensor), None: sample j is row j.  N is at most 4096.
+    The table, the colours and host indices travel in one non-blocking copy; no host read, no synchronisation.
+    Returns dict(frames: the per-frame [H, W, 3] views, point_rows, point_count, point_class_range)."""
+    from . import data as _data
+    style = ScatterStyle() if style is None else style
+    lib = _pass_lib(arena)
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError("scatter_points_frames: `arena` is a contiguous 1-D uint8 tensor")
+    dev = arena.device
+    if point_class.dim() != 2 or point_class.dtype.is_floating_point or point_class.device != dev:
+        raise ValueError("scatter_points_frames: point_class is an integer tensor [B, N] on the arena's device")
+    B, N = (int(v) for v in point_class.shape)
+    if not 1 <= N <= SCATTER_MAX_POINTS:
+        raise ValueError(f"scatter_points_frames: 1..{SCATTER_MAX_POINTS} points per frame, got {N}")
+    cls = point_class.to(torch.int64).contiguous()
+    shapes = _frame_shapes(shapes, B)
+    offs, pitches = (layout[3], layout[4]) if len(layout) == 6 else layout
+    if len(offs) != B or len(pitches) != B:
+        raise ValueError("scatter_points_frames: one offset and one pitch per frame")
+    table = np.zeros((B, SCATTER_TABLE_COLS), np.int64)
+    if isinstance(points, torch.Tensor):
+        if tuple(points.shape) != (B, N, 3) or points.dtype not in (torch.float32, torch.float64) or points.device != dev:
+            raise ValueError("scatter_points_frames: dense points are a float32 / float64 tensor [B, N, 3] = (u, v, size) on the arena's device")
+        cloud = points.contiguous()
+        for b in range(B):
+            table[b, 4:11] = (b * N * 3, N, 3, 3, 0, 1, 2)
+    else:
+        packed = _data._as_clouds(points, dev, 'scatter_clouds')
+        cloud = packed.data
+        if len(packed.frames) != B or cloud.device != dev:
+            raise ValueError(f"scatter_points_frames: one cloud per frame on the arena's device expected, got {len(packed.frames)} for {B} frames")
+        rcs, cu, cv = _columns or style.columns or _data.MAP_COLUMNS[2:5]
+        for b, fr in enumerate(packed.frames):
+            table[b, 4:11] = tuple(fr) + (cu, cv, rcs)
+    for b, (h, w) in enumerate(shapes):
+        table[b, :4] = (int(offs[b]), h, w, int(pitches[b]))
+    colours, mode, lo, hi = style.table(int(num_classes))
+    meta = _data._Meta(dev, 'serve_scatter')
+    tref, cref, iref = meta.add(table), meta.add(colours), None
+    idx_dev = None
+    if isinstance(indices, torch.Tensor) and indices.device.type != 'cpu':
+        if tuple(indices.shape) != (B, N) or indices.device != dev:
+            raise ValueError("scatter_points_frames: indices are [B, N] on the arena's device or on the host")
+        idx_dev = indices.to(torch.int64).contiguous()
+    elif indices is not None:
+        idx = np.ascontiguousarray(indices.numpy() if isinstance(indices, torch.Tensor) else indices, dtype=np.int64)
+        if idx.shape != (B, N):
+            raise ValueError(f"scatter_points_frames: indices are [B, N] = [{B}, {N}]")
+        iref = meta.add(idx)
+    meta.commit()
+    rows = torch.empty(B, N, 4, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    rng = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    discs = torch.empty(B * N * 4, dtype=torch.float64, device=dev)
+    boxes = torch.empty(B * N * 4, dtype=torch.int32, device=dev)
+    ctx = torch.cuda.device(dev) if arena.is_cuda else contextlib.nullcontext()
+    with ctx:
+        _check(lib, lib.lib.ach_scatter_points_frames(_ptr(arena), arena.numel(), meta.host_ptr(tref), meta.dev_ptr(tref), B, _ptr(cloud), cloud.numel(),
+                                                      0 if cloud.dtype == torch.float32 else 1, _ptr(idx_dev) if iref is None else meta.dev_ptr(iref), _ptr(cls), N,
+                                                      int(num_classes), meta.dev_ptr(cref), mode, lo, hi, style.alpha, style.k, style.max_radius, _ptr(rows), _ptr(count),
+                                                      _ptr(rng), _ptr(discs), discs.numel() * 8, _ptr(boxes), boxes.numel() * 4, _stream(arena)),
+               _DRAW_ERRORS, 'scatter kernels')
+    return {'frames': [torch.as_strided(arena, (h, w, 3), (int(pitches[b]), 3, 1), int(offs[b])) for b, (h, w) in enumerate(shapes)],
+            'point_rows': rows, 'point_count': count, 'point_class_range': rng}
+
+
 def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4, letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True,
-                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3, draw=None, heatmap=None):
+                  palette_se=PALETTE_SEG, palette_line=PALETTE_LINE, keep_classes=None, blend=(0.45, 0.3), brightness=1.3, draw=None, heatmap=None, scatter=None,
+                  point_uvs=None):
     """`detect_frame` for B frames of DIFFERENT sizes: the arithmetic of the reference's detect_image (achelous.py:190-433) without its file I/O; the box drawing
     (achelous.py:363-433) is on with `draw`.
 
@@ -665,27 +803,36 @@ def detect_frames(net, frames, radar_maps, points, conf_thres=0.5, nms_thres=0.4
     is required), and the result gains class_counts [B, num_classes] int32, the kept rows per class id.  With draw=None nothing changes.
     heatmap: None, or a `HeatmapStyle` — three more launches (`heatmap_frames`) on the det maps of the same `forward_detect`, and the result gains heat_mask,
     heat_range and heatmap; the colour goes over the camera frames (style.over = 'frame', the reference) or over the overlay as it is after the drawing ('overlay',
-    needs overlay=True), into an arena of its own: every other key is what it is without `heatmap`, and with heatmap=None nothing changes."""
+    needs overlay=True), into an arena of its own: every other key is what it is without `heatmap`, and with heatmap=None nothing changes.
+    scatter: None, or a `ScatterStyle` — two more launches (`scatter_points_frames`) paint the radar point classes on the overlay (overlay=True is required) after the
+    drawing and before a heat map with over='overlay', as the reference's scatter lies above the image with its boxes; `point_uvs` [B, N, 3] float32 / float64 on the
+    device holds every point's (u, v, size) in the frame's own pixels.  The result gains point_rows, point_count and point_class_range; with scatter=None nothing changes."""
     from . import data as _data
-    _need_overlay(draw, overlay, heatmap)
+    _need_overlay(draw, overlay, heatmap, scatter)
+    if scatter is not None and point_uvs is None:
+        raise ValueError("detect_frames: `scatter` needs `point_uvs` [B, N, 3] = (u, v, size)")
     R = net.resolution
     arena = _data._as_arena(frames, 3, radar_maps.device, 'images')
     B = len(arena.frames)
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = preprocess_input_radar(radar_maps, dtype)
     xp = normalize_points(points, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap,
+                            scatter, (point_uvs, None, None))
 
 
-def _need_overlay(draw, overlay, heatmap=None):
+def _need_overlay(draw, overlay, heatmap=None, scatter=None):
+    if scatter is not None and not overlay:
+        raise ValueError("detect_frames: `scatter` paints on the overlay, so it needs overlay=True")
     if draw is not None and not overlay:
         raise ValueError("detect_frames: `draw` draws on the overlay, so it needs overlay=True")
     if heatmap is not None and heatmap.over == 'overlay' and not overlay:
         raise ValueError("detect_frames: `heatmap` with over='overlay' colours the overlay, so it needs overlay=True")
 
 
-def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw=None, heatmap=None):
-    """`detect_frames` from the three prepared network inputs on"""
+def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw=None, heatmap=None,
+                     scatter=None, scatter_source=None):
+    """`detect_frames` from the three prepared network inputs on; scatter_source: (points, indices, columns) as `scatter_points_frames` takes them"""
     R, B = net.resolution, len(arena.frames)
     shapes = [(f[1], f[2]) for f in arena.frames]
     (det, se, lane, pc), (rows, idx, cnt) = net.forward_detect(x, xr, xp, conf_thres, nms_thres, max_det)
@@ -698,6 +845,10 @@ def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_ima
     if draw is not None:
         res['class_counts'] = torch.empty(B, len(draw.class_names), dtype=torch.int32, device=boxes.device)
         draw_detections_frames(maps['arenas']['overlay'], frames_layout(shapes), boxes, cnt, shapes, draw, (R, R), res['class_counts'])
+    if scatter is not None:
+        pts = scatter_points_frames(maps['arenas']['overlay'], frames_layout(shapes), shapes, scatter_source[0], res['point_class'], int(pc.shape[-1]), scatter,
+                                    scatter_source[1], _columns=scatter_source[2])
+        res.update({k: pts[k] for k in ('point_rows', 'point_count', 'point_class_range')})
     if heatmap is not None:
         under = (maps['arenas']['overlay'], frames_layout(shapes)) if heatmap.over == 'overlay' else (arena, None)
         heat = heatmap_frames(det, shapes, under[0], under[1], heatmap, (R, R), letterbox_image)
@@ -707,14 +858,16 @@ def _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_ima
 
 def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_points=512, columns=None, point_columns=None, cell=None, conf_thres=0.5, nms_thres=0.4,
                               letterbox_image=True, max_det=100, dtype=torch.bfloat16, overlay=True, palette_se=PALETTE_SEG, palette_line=PALETTE_LINE,
-                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda', draw=None, heatmap=None):
+                              keep_classes=None, blend=(0.45, 0.3), brightness=1.3, device='cuda', draw=None, heatmap=None, scatter=None):
     """`detect_frames` from raw radar point clouds instead of ready radar maps and sampled points: `clouds` is a list of CPU float32 / float64 arrays [n_i, F] (or
     `data.Clouds` already on the device), uploaded once.  The normalised radar map is `data.radar_maps_batch(..., normalize=True)` (the reference's offline
     rasterisation, then its min-max scaling: `columns` = the columns of range, doppler, rcs, u, v, default 0..4; `cell` default (6.0, 3.375)); the points are
     `data.radar_points_batch`: `num_points` rows per frame by `indices` [B, N] or drawn from `rng`, the columns `point_columns` (default: the first
-    `net.pc_channels`), normalised.  Two launches for the map and one for the points whatever B is, nothing read back; everything else and the result as `detect_frames`."""
+    `net.pc_channels`), normalised.  Two launches for the map and one for the points whatever B is, nothing read back; everything else and the result as `detect_frames`.
+    scatter: None, or a `ScatterStyle` — the point classes painted on the overlay (`scatter_points_frames`, two more launches) from the packed clouds themselves: the
+    rows the points were sampled by (`indices`, or the ones drawn from `rng`) and the rcs, u, v columns of `columns` (or style.columns)."""
     from . import data as _data
-    _need_overlay(draw, overlay, heatmap)
+    _need_overlay(draw, overlay, heatmap, scatter)
     R = net.resolution
     packed = _data._as_clouds(clouds, device)
     arena = _data._as_arena(frames, 3, packed.data.device, 'images')
@@ -723,5 +876,10 @@ def detect_frames_from_clouds(net, frames, clouds, indices=None, rng=None, num_p
         raise ValueError(f"detect_frames_from_clouds: one cloud per frame expected, got {len(packed.frames)} for {B} frames")
     x = _data.letterbox_batch(arena, R, None if letterbox_image else [(R, R, 0, 0)] * B, dtype)
     xr = _data.radar_maps_batch(packed, R, _data.MAP_COLUMNS if columns is None else columns, _data.CELL if cell is None else cell, True, dtype)
+    source = None
+    if scatter is not None:                                              # the rows the points are sampled by, drawn here so that the scatter reads the same ones
+        indices = _data.draw_indices([f[1] for f in packed.frames], num_points, indices, rng)
+        source = (packed, indices, scatter.columns or tuple((_data.MAP_COLUMNS if columns is None else columns)[2:5]))
     xp, _ = _data.radar_points_batch(packed, tuple(range(net.pc_channels)) if point_columns is None else point_columns, None, num_points, indices, rng, dtype)
-    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap)
+    return _detect_prepared(net, arena, x, xr, xp, conf_thres, nms_thres, letterbox_image, max_det, overlay, palette_se, palette_line, keep_classes, blend, brightness, draw, heatmap,
+                            scatter, source)
