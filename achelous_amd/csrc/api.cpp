@@ -12,7 +12,7 @@ extern "C" {
 int ach_create(const ach_config* cfg, ach_handle** out) {
     if (!cfg || !out) return ACH_ERR_INVALID;
     try {
-        if (cfg->backbone != ACH_BACKBONE_EDGENEXT && cfg->backbone != ACH_BACKBONE_MOBILEVIT && cfg->backbone != ACH_BACKBONE_POOLFORMER)
+        if (cfg->backbone != ACH_BACKBONE_EDGENEXT && cfg->backbone != ACH_BACKBONE_MOBILEVIT && cfg->backbone != ACH_BACKBONE_POOLFORMER && cfg->backbone != ACH_BACKBONE_REPVIT)
             throw ach::AchError{ACH_ERR_UNSUPPORTED, "backbone must be 'en' or 'mv'"};
         if (cfg->phi < ACH_PHI_S0 || cfg->phi > ACH_PHI_S2) throw ach::AchError{ACH_ERR_UNSUPPORTED, "phi must be S0, S1 or S2"};
         if (cfg->neck != ACH_NECK_GDF && cfg->neck != ACH_NECK_CDF) throw ach::AchError{ACH_ERR_UNSUPPORTED, "neck must be 'gdf' or 'cdf'"};

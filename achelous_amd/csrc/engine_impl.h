@@ -26,6 +26,7 @@
 #include "k_pn2.h"
 #include "k_prepost.h"
 #include "k_radar.h"
+#include "k_repvit.h"
 #include <functional>
 #include "k_sdta.h"
 #include "k_xca.h"
@@ -1118,6 +1119,151 @@ public:
             feats[i] = out;
             if (i < 3) reached(Point(kPtStage0 + i));
         }
+    }
+
+    // ------------------------------------------------------------------------------------------ RepViT (k_repvit.h)
+    // BatchNorm as y = s x + t, in double: s = gamma / sqrt(var + eps), t = beta - mean s
+    void bn_coeffs_d(const std::string& pfx, double eps, std::vector<double>& s, std::vector<double>& t) const {
+        const auto& g = W(pfx + ".weight").data; const auto& b = W(pfx + ".bias").data;
+        const auto& m = W(pfx + ".running_mean").data; const auto& v = W(pfx + ".running_var").data;
+        if (b.size() != g.size() || m.size() != g.size() || v.size() != g.size()) throw AchError{ACH_ERR_MISSING_KEY, "BatchNorm shapes at " + pfx};
+        s.resize(g.size()); t.resize(g.size());
+        for (size_t i = 0; i < g.size(); ++i) { s[i] = double(g[i]) / std::sqrt(double(v[i]) + eps); t[i] = double(b[i]) - double(m[i]) * s[i]; }
+    }
+    // Conv2d_BN (repvit.py: conv without bias + BatchNorm2d, eps 1e-5) as one linear map: rows scaled by s, bias t.  `l` holds the conv's matrix (1x1 or implicit-GEMM layout)
+    void fold_conv2d_bn(Lin& l, const std::string& pfx) const {
+        std::vector<double> sc, sh; bn_coeffs_d(pfx + ".bn", 1e-5, sc, sh);
+        if (int(sc.size()) != l.N) throw AchError{ACH_ERR_MISSING_KEY, "BatchNorm width mismatch at " + pfx};
+        for (int n = 0; n < l.N; ++n) {
+            for (int k = 0; k < l.K; ++k) l.w[size_t(n) * l.K + k] = float(double(l.w[size_t(n) * l.K + k]) * sc[n]);
+            l.b[n] = float(sh[n]);
+        }
+    }
+    // the depthwise 3x3 of a block as [9][C] weights + bias.  Stride 2: Conv2d_BN.  Stride 1 (RepVGGDW: BN(dw3x3 x) + BN(dw1x1 x) + x): ONE 3x3 whose centre tap gains s1 w1x1 + 1
+    void rv_dw_weights(const std::string& tm, int C, int stride, std::vector<float>& wt, std::vector<float>& bias) const {
+        const std::string c3 = stride == 2 ? tm + ".0" : tm + ".0.conv";
+        const HostTensor& w3 = W(c3 + ".c.weight");
+        if (w3.numel() != long(C) * 9) throw AchError{ACH_ERR_MISSING_KEY, "depthwise shape at " + c3};
+        std::vector<double> s3, t3, s1, t1;
+        bn_coeffs_d(c3 + ".bn", 1e-5, s3, t3);
+        if (int(s3.size()) != C) throw AchError{ACH_ERR_MISSING_KEY, "BatchNorm width mismatch at " + c3};
+        wt.assign(size_t(9) * C, 0.f); bias.assign(size_t(C), 0.f);
+        const HostTensor* w1 = nullptr;
+        if (stride == 1) {
+            w1 = &W(tm + ".0.conv1.c.weight");
+            bn_coeffs_d(tm + ".0.conv1.bn", 1e-5, s1, t1);
+            if (w1->numel() != long(C) || int(s1.size()) != C) throw AchError{ACH_ERR_MISSING_KEY, "depthwise 1x1 shape at " + tm};
+        }
+        for (int c = 0; c < C; ++c) {
+            for (int t = 0; t < 9; ++t) {
+                double v = s3[size_t(c)] * double(w3.data[size_t(c) * 9 + t]);
+                if (stride == 1 && t == 4) v += s1[size_t(c)] * double(w1->data[size_t(c)]) + 1.0;
+                wt[size_t(t) * C + c] = float(v);
+            }
+            bias[size_t(c)] = float(t3[size_t(c)] + (stride == 1 ? t1[size_t(c)] : 0.0));
+        }
+    }
+    // `dst[k]` (optional, may be null): where the block whose output is map k writes it
+    void repvit(const std::string& pfx, A feats[4], const A* const dst[4]) {                     // repvit.py RepViT.forward; cfg rows as in achelous_amd/spec.py REPVIT
+        // per stage: the stride-1 rows' SE flags, first row first ('d' = the stride-2 row that opens stages 1..3); the features indices of the four maps
+        static const char* kStages[3][4] = {{"100", "d100", "d101010101010100", "d10"}, {"100", "d100", "d1010101010100", "d10"}, {"10100", "d10100", "d1010101010101010100", "d10"}};
+        static const int kOut[3][4] = {{2, 6, 22, 25}, {2, 6, 20, 24}, {4, 10, 30, 34}};
+        const int ph = cfg.phi == ACH_PHI_S0 ? 0 : (cfg.phi == ACH_PHI_S1 ? 1 : 2);
+        const int* wd = widths();
+        const int B = batch, R = cfg.resolution;
+        A x;
+        {   // features[0]: conv3x3 s2 + BN, GELU (rv_stem_kernel, from the NCHW image), conv3x3 s2 + BN (implicit GEMM)
+            const std::string a = pfx + ".features.0.0", c = pfx + ".features.0.2";
+            const HostTensor& w = W(a + ".c.weight");
+            if (w.shape.size() != 4 || w.shape[0] != RV_STEM_C || w.shape[1] != 3 || w.shape[2] != 3 || w.shape[3] != 3 || wd[0] != 2 * RV_STEM_C) throw AchError{ACH_ERR_UNSUPPORTED, "RepViT stem shape"};
+            Lin la; la.N = RV_STEM_C; la.K = 27; la.w = w.data; la.b.assign(RV_STEM_C, 0.f);
+            fold_conv2d_bn(la, a);
+            std::vector<float> wt(size_t(28) * RV_STEM_C, 0.f);
+            for (int n = 0; n < RV_STEM_C; ++n) { for (int k = 0; k < 27; ++k) wt[size_t(k) * RV_STEM_C + n] = la.w[size_t(n) * 27 + k]; wt[size_t(27) * RV_STEM_C + n] = la.b[n]; }
+            const int Ho = (R - 1) / 2 + 1;
+            A y = alloc(B, Ho, Ho, RV_STEM_C);
+            RvStemParams sp{nullptr, y.p, up_f32(wt), R, R, Ho, Ho};
+            const dim3 grid(unsigned(cdiv(Ho * Ho, 256)), unsigned(B)), block(256);
+            const void** img = &io.image;
+            const bool alt = io_alt();
+            add_op(a, [sp, grid, block, img, alt](hipStream_t s) mutable { sp.X = *img; if (alt) ACH_LAUNCH((rv_stem_kernel<T, IOB>), grid, block, s, sp); else ACH_LAUNCH((rv_stem_kernel<T, T>), grid, block, s, sp); },
+                   (double(B) * 3 * R * R + double(y.rows()) * RV_STEM_C) * sizeof(T), 2.0 * double(y.rows()) * 27 * RV_STEM_C);
+            Lin lc = conv_lin(c + ".c.weight", "", RV_STEM_C, int(y.ld), 3);
+            if (lc.N != wd[0]) throw AchError{ACH_ERR_MISSING_KEY, "RepViT stem width at " + c};
+            fold_conv2d_bn(lc, c);
+            x = conv_gemm(c, y, lc, 3, 2, ACT_NONE);
+            tap("backbone.f0", x);
+        }
+        int idx = 0, nmap = 0;
+        for (int st = 0; st < 4 && nmap < 4; ++st) {
+            for (const char* r = kStages[ph][st]; *r && nmap < 4; ++r) {        // (the blocks behind the last map are dead: not run)
+                ++idx;
+                const std::string bp = pfx + ".features." + std::to_string(idx), tm = bp + ".token_mixer", cm = bp + ".channel_mixer.m";
+                const int stride = *r == 'd' ? 2 : 1, inp = x.C, C = wd[st];
+                const bool se = *r == '1';
+                if (inp % 8 != 0 || C % 8 != 0 || x.ld % VEC != 0 || (stride == 1 && inp != C)) throw AchError{ACH_ERR_UNSUPPORTED, "RepViT block width at " + bp};
+                // ---- token mixer: one depthwise 3x3 [+ SE gate] [stride 2: + 1x1 inp -> oup]
+                std::vector<float> wt, bs;
+                rv_dw_weights(tm, inp, stride, wt, bs);
+                const int Ho = (x.H - 1) / stride + 1, Wo = (x.W - 1) / stride + 1, HW = Ho * Wo;
+                A d = alloc(B, Ho, Wo, inp);
+                RvDwParams dp{x.p, x.ld, d.p, d.ld, up_f32(wt), up_f32(bs), nullptr, x.H, x.W, Ho, Wo, inp, rv_dw_band(Ho)};
+                const int P = cdiv(Ho, dp.RB);
+                if (se) dp.psum = alloc_f32(size_t(B) * P * inp);
+                add_op(tm + ".dw", [dp, stride, se, B](hipStream_t s) { launch_rv_dw3<T>(dp, stride, se, B, s); }, (double(x.rows()) + double(d.rows())) * inp * sizeof(T), 18.0 * double(d.rows()) * inp);
+                const float* gate = nullptr;
+                if (se) {   // the reduced width is whatever fc1.weight says (timm versions round C / 4 differently)
+                    const HostTensor& f1 = W(tm + ".1.fc1.weight"); const HostTensor& f2 = W(tm + ".1.fc2.weight");
+                    const int RD = f1.shape.empty() ? 0 : int(f1.shape[0]);
+                    const auto& b1 = W(tm + ".1.fc1.bias").data; const auto& b2 = W(tm + ".1.fc2.bias").data;
+                    if (RD < 1 || RD > RV_SE_RMAX || inp > RV_SE_CMAX || f1.numel() != long(RD) * inp || f2.numel() != long(RD) * inp || int(b1.size()) != RD || int(b2.size()) != inp)
+                        throw AchError{ACH_ERR_UNSUPPORTED, "RepViT SqueezeExcite shapes at " + tm};
+                    std::vector<float> w1t(size_t(inp) * RD), w2t(size_t(RD) * inp);
+                    for (int rr = 0; rr < RD; ++rr)
+                        for (int c = 0; c < inp; ++c) { w1t[size_t(c) * RD + rr] = f1.data[size_t(rr) * inp + c]; w2t[size_t(rr) * inp + c] = f2.data[size_t(c) * RD + rr]; }
+                    float* gp = alloc_f32(size_t(B) * inp);
+                    RvGateParams gq{dp.psum, P, 1.0f / float(HW), up_f32(w1t), up_f32(b1), up_f32(w2t), up_f32(b2), gp, inp, RD};
+                    add_op(tm + ".gate", [gq, B](hipStream_t s) { ACH_LAUNCH(rv_gate_kernel<T>, dim3(unsigned(B)), dim3(256), s, gq); }, double(B) * P * inp * 4.0, 4.0 * double(B) * inp * RD);
+                    gate = gp;
+                }
+                if (stride == 2) {
+                    Lin lp = lin(tm + ".2.c.weight", "");
+                    if (lp.K != inp || lp.N != C) throw AchError{ACH_ERR_MISSING_KEY, "RepViT down-sampling width at " + tm};
+                    fold_conv2d_bn(lp, tm + ".2");
+                    A t = alloc(B, Ho, Wo, C);
+                    gemm(tm + ".pw", d, pack(lp), t, GemmOpt());
+                    d = t;
+                }
+                // ---- channel mixer: y = g.d + W2 GELU(W1 (g.d) + b1) + b2, hidden 2C
+                Lin l1 = lin(cm + ".0.c.weight", ""); fold_conv2d_bn(l1, cm + ".0");
+                Lin l2 = lin(cm + ".2.c.weight", ""); fold_conv2d_bn(l2, cm + ".2");
+                const int DT = mlp_pick_dt(C);
+                if (DT == 0 || DT > 18 || l1.K != C || l2.N != C || l2.K != l1.N) throw AchError{ACH_ERR_UNSUPPORTED, "RepViT MLP shapes at " + bp};
+                const bool is_map = idx == kOut[ph][nmap];
+                A z;
+                if (is_map && dst && dst[nmap]) {
+                    z = *dst[nmap];
+                    reached(kPtConcatSlice);        // (the next launch writes a slice of the neck's concat buffer)
+                    if (z.B != d.B || z.H != d.H || z.W != d.W || z.C != C || z.ld % 8 != 0) throw AchError{ACH_ERR_INVALID, "RepViT output destination does not match the block"};
+                } else z = alloc(B, Ho, Wo, C);
+                RvMlpParams q;
+                std::memset(&q, 0, sizeof(q));
+                chain_weights(q.m, C, DT, l1, ACT_GELU, l2);
+                q.m.X = d.p; q.m.ldx = d.ld; q.m.Y = z.p; q.m.ldy = z.ld; q.m.M = d.rows();
+                q.gate = gate; q.HW = HW;
+                // per-sample map size, not batch, decides the geometry (as for mlp_kernel): four waves per tile on the small maps
+                const bool split = mlp_split < 0 ? HW <= mlp_split_hw : mlp_split != 0;
+                add_op(bp + ".mlp", [q, DT, split, B](hipStream_t s) { launch_rv_mlp<T>(q, DT, split, B, s); }, 2.0 * double(d.rows()) * C * sizeof(T), 4.0 * double(d.rows()) * C * l1.N);
+                tap("backbone.f" + std::to_string(idx), z);
+                x = z;
+                if (is_map) {
+                    feats[nmap] = z;
+                    if (nmap < 3) reached(Point(kPtStage0 + nmap));
+                    ++nmap;
+                }
+            }
+        }
+        if (nmap != 4) throw AchError{ACH_ERR_INVALID, "RepViT: fewer than four maps"};
     }
 
     // ------------------------------------------------------------------------------------------ neck (a7-a13)
@@ -2307,6 +2453,16 @@ public:
             const A d1 = cat_buf[0].slice(wd[1], wd[1]), d2 = cat_buf[1].slice(wd[2], wd[2]);
             const A* dst[4] = {nullptr, &d1, &d2, nullptr};
             poolformer("image_radar_encoder.fpn.backbone", m, dst);
+        }
+        else if (cfg.backbone == ACH_BACKBONE_REPVIT) {
+            // the same direct write: the blocks whose outputs are map3 / map4 store them in the neck's concat buffers (and the next block reads them there)
+            const int* wd = widths();
+            const int R = cfg.resolution;
+            cat_buf[0] = alloc(batch, R / 8, R / 8, 2 * wd[1]);
+            cat_buf[1] = alloc(batch, R / 16, R / 16, 2 * wd[2]);
+            const A d1 = cat_buf[0].slice(wd[1], wd[1]), d2 = cat_buf[1].slice(wd[2], wd[2]);
+            const A* dst[4] = {nullptr, &d1, &d2, nullptr};
+            repvit("image_radar_encoder.fpn.backbone", m, dst);
         }
         else mobilevit("image_radar_encoder.fpn.backbone", m);
         A q[3];

@@ -35,7 +35,8 @@ template <class Engine> Schedule make_schedule(const Engine& e) {
     Schedule s;
     constexpr auto bit = [](int event) { return static_cast<unsigned char>(1u << event); };
     // (PoolFormer is one in-order segment on the caller's stream like the other two and takes the MobileViT side of both decisions below: its stage outputs are fork-norm
-    //  launches, not the preset block outputs the neck-on-stream-2 plan orders against; its direct write into the neck's concat buffers is the engine's business, not the schedule's)
+    //  launches, not the preset block outputs the neck-on-stream-2 plan orders against; its direct write into the neck's concat buffers is the engine's business, not the schedule's.
+    //  RepViT likewise: one in-order segment, the MobileViT side, maps 2 .. 4 announced as stages 0 .. 2)
     const bool edgenext = e.cfg.backbone == ACH_BACKBONE_EDGENEXT, pn2 = e.cfg.pc_seg == ACH_PCSEG_PN2 || e.cfg.pc_seg == ACH_PCSEG_PN2_MSG;
     const bool piped = e.pipeline && e.multi_stream && e.split_decoders == 0;      // the pipelined plan proper: the decoders leave the caller's stream together
     // radar release.  -2 (default) = stage 2 in the pipelined plan, else 1.  EdgeNeXt records it at stage `radar_start` exactly, so 4 and above record nothing and the plan fails in

@@ -15,7 +15,7 @@ HIP_LIBRARY = os.path.join(_HERE, 'libachelous_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'achelous.h')
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # include/achelous.h ACH_DTYPE_*: storage type of the activations (F16: inputs / outputs fp16, or bf16 with option io_bf16)
-BACKBONES = {'en': 0, 'mv': 1, 'pf': 2}
+BACKBONES = {'en': 0, 'mv': 1, 'pf': 2, 'rv': 4}       # (3 is reserved for the reference's default 'ef' and refused)
 PHIS = {'S0': 0, 'S1': 1, 'S2': 2}
 NECKS = {'gdf': 0, 'cdf': 1}
 PC_SEGS = {'pn': 0, 'pn2': 1, 'none': 2, 'pn2_msg': 3}     # 'none': Achelous3T (nets/Achelous.py:56-76), no point stream

@@ -100,8 +100,8 @@ def _check_supported(backbone, neck, pc_seg, phi, num_seg, image_channels, radar
     """ONE error that lists every constructor argument outside the built path — the reference's own defaults
     (`backbone='ef'`, nets/Achelous.py:27) are among them."""
     bad = []
-    if backbone not in ('en', 'mv', 'pf'):
-        bad.append(f"backbone={backbone!r} (built: 'en' EdgeNeXt, 'mv' MobileViT, 'pf' PoolFormer; the reference default 'ef' and the other five backbones are out of scope)")
+    if backbone not in ('en', 'mv', 'pf', 'rv'):
+        bad.append(f"backbone={backbone!r} (built: 'en' EdgeNeXt, 'mv' MobileViT, 'pf' PoolFormer, 'rv' RepViT; the reference default 'ef' and the other four backbones are out of scope)")
     if neck not in ('gdf', 'cdf'):
         bad.append(f"neck={neck!r} (built: 'gdf' Ghost-Dual-FPN, 'cdf' CSP-Dual-FPN)")
     if pc_seg not in ('pn', 'pn2', 'pn2_msg', 'none'):
@@ -178,7 +178,7 @@ class Achelous(nn.Module):
     def train(self, mode=True):
         # PoolFormer is built for inference only: no GroupNorm(1) backward kernels exist, and the training graph must not fall into EdgeNeXt code
         if mode and self.__dict__.get('backbone') == 'pf':
-            raise NotImplementedError("achelous_amd.Achelous: training mode is not built for backbone='pf' (PoolFormer is inference only; 'en' and 'mv' train)")
+            raise NotImplementedError("achelous_amd.Achelous: training mode is not built for backbone='pf' (PoolFormer is inference only; 'en', 'mv' and 'rv' train)")
         return super().train(mode)
 
     def _init_like_reference(self):
@@ -228,9 +228,28 @@ class Achelous(nn.Module):
         self.__dict__['_wt_list'] = None
         return super()._apply(fn, *a, **k)
 
-    def load_state_dict(self, *a, **k):
+    def load_state_dict(self, state_dict, *a, **k):
         self.__dict__['_wt_list'] = None
-        return super().load_state_dict(*a, **k)
+        if self.__dict__.get('backbone') == 'rv':
+            self._adopt_se_widths(state_dict)
+        return super().load_state_dict(state_dict, *a, **k)
+
+    def _adopt_se_widths(self, state_dict):
+        """RepViT's SqueezeExcite reduced width is whatever the checkpoint's `fc1.weight` says (timm versions round C / 4 differently: to the nearest integer, or to
+        a multiple of 8); the engine reads it from the shape too.  The three parameters whose shape depends on it are re-made to match before loading."""
+        for key, v in state_dict.items():
+            if not key.endswith('.token_mixer.1.fc1.weight') or v.dim() != 4:
+                continue
+            try:
+                se = self.get_submodule(key[:-len('.fc1.weight')])
+            except AttributeError:
+                continue
+            rd, c = int(v.shape[0]), int(se.fc1.weight.shape[1])
+            if rd != se.fc1.weight.shape[0] and rd >= 1 and v.shape[1] == c:
+                like = se.fc1.weight
+                se.fc1.weight = nn.Parameter(torch.zeros(rd, c, 1, 1, dtype=like.dtype, device=like.device))
+                se.fc1.bias = nn.Parameter(torch.zeros(rd, dtype=like.dtype, device=like.device))
+                se.fc2.weight = nn.Parameter(torch.zeros(c, rd, 1, 1, dtype=like.dtype, device=like.device))
 
     def native_engine(self, dtype=torch.float32, device=None):
         """The engine that served the last forward of this dtype on `device` (tests, bench: taps, launch table, options)."""

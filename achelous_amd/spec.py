@@ -22,6 +22,24 @@ MOBILEVIT = {  # backbone/vision/mobilevit_modules/mobilevit.py:225-240
     'S2': dict(dims=[144, 192, 240], ch=[16, 32, 32, 32, 64, 64, 144, 144, 144, 144, 288], exp=4),
 }
 POOLFORMER = {'S0': [2, 2, 6, 2], 'S1': [4, 4, 12, 4], 'S2': [6, 6, 18, 6]}   # poolformer_modules/poolformer.py poolformer_S0/S1/S2: block depths; the widths are WIDTHS[phi]
+# repvit_modules/repvit.py repvit_m1 / m2 / m3: per stage one character per cfg row — 'd' the stride-2 row that opens the stage (never SE), '1' / '0' a stride-1 row
+# with / without SqueezeExcite; features[0] is the stem, row r is features[r + 1].  `out`: the features indices returned as map2..map5 (NOT the stage ends; blocks
+# behind the last one are dead in inference).  Widths are WIDTHS[phi], hidden 2C, every kernel 3x3.
+REPVIT = {
+    'S0': dict(stages=['100', 'd100', 'd' + '10' * 7 + '0', 'd10'], out=[2, 6, 22, 25]),
+    'S1': dict(stages=['100', 'd100', 'd' + '10' * 6 + '0', 'd10'], out=[2, 6, 20, 24]),
+    'S2': dict(stages=['10100', 'd10100', 'd' + '10' * 9 + '0', 'd10'], out=[4, 10, 30, 34]),
+}
+
+
+def repvit_rows(phi):
+    """[(inp, oup, stride, se)] for features[1:], in order."""
+    rows, inp = [], WIDTHS[phi][0]
+    for c, stage in zip(WIDTHS[phi], REPVIT[phi]['stages']):
+        for ch in stage:
+            rows.append((inp, c, 2 if ch == 'd' else 1, ch == '1'))
+            inp = c
+    return rows
 
 
 class _Spec(list):
@@ -250,7 +268,32 @@ def _poolformer(s, pfx, phi):                   # poolformer_modules/poolformer.
         s.ln(f'{pfx}.norm{2 * i}', dims[i])
 
 
-_BACKBONES = {'en': _edgenext, 'mv': _mobilevit, 'pf': _poolformer}
+def _conv2d_bn(s, pfx, cout, cin, k):           # repvit.py Conv2d_BN: conv (no bias) + BatchNorm2d
+    s.p(pfx + '.c.weight', cout, cin, k, k)
+    s.bn(pfx + '.bn', cout)
+
+
+def _repvit(s, pfx, phi):                       # repvit_modules/repvit.py RepViT (no classifier); SE = timm SqueezeExcite(C, 0.25): reduced width round(C / 4), 1x1 convs WITH bias
+    c0 = WIDTHS[phi][0]
+    _conv2d_bn(s, f'{pfx}.features.0.0', c0 // 2, 3, 3)
+    _conv2d_bn(s, f'{pfx}.features.0.2', c0, c0 // 2, 3)
+    for i, (inp, oup, stride, se) in enumerate(repvit_rows(phi), 1):
+        b = f'{pfx}.features.{i}'
+        if stride == 2:
+            _conv2d_bn(s, b + '.token_mixer.0', inp, 1, 3)
+            _conv2d_bn(s, b + '.token_mixer.2', oup, inp, 1)
+        else:
+            _conv2d_bn(s, b + '.token_mixer.0.conv', inp, 1, 3)
+            _conv2d_bn(s, b + '.token_mixer.0.conv1', inp, 1, 1)
+            if se:
+                rd = max(1, int(round(inp * 0.25)))
+                s.wb(b + '.token_mixer.1.fc1', (rd, inp, 1, 1))
+                s.wb(b + '.token_mixer.1.fc2', (inp, rd, 1, 1))
+        _conv2d_bn(s, b + '.channel_mixer.m.0', 2 * oup, oup, 1)
+        _conv2d_bn(s, b + '.channel_mixer.m.2', oup, 2 * oup, 1)
+
+
+_BACKBONES = {'en': _edgenext, 'mv': _mobilevit, 'pf': _poolformer, 'rv': _repvit}
 
 
 def _ghost(s, pfx, inp, oup):                   # ghost_conv.py:6-23
@@ -397,7 +440,7 @@ def state_dict_spec(num_det, num_seg, phi='S0', backbone='en', pc_channels=6, pc
     if pc_seg not in ('pn', 'pn2', 'pn2_msg', 'none'):
         raise NotImplementedError(f"pc_seg={pc_seg!r}: 'pn' (reference), 'pn2' / 'pn2_msg' (own specifications) and 'none' (Achelous3T, nets/Achelous.py:56-76) are built")
     if phi not in WIDTHS or backbone not in _BACKBONES or neck not in ('gdf', 'cdf'):
-        raise NotImplementedError(f"backbone={backbone!r}, phi={phi!r}, neck={neck!r}: only 'en'/'mv'/'pf' with S0/S1/S2 and gdf/cdf are built")
+        raise NotImplementedError(f"backbone={backbone!r}, phi={phi!r}, neck={neck!r}: only 'en'/'mv'/'pf'/'rv' with S0/S1/S2 and gdf/cdf are built")
     s = _Spec()
     if pc_seg != 'none':
         if pc_seg == 'pn':

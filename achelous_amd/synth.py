@@ -23,6 +23,10 @@ def _rng(seed, key):
     return np.random.Generator(np.random.PCG64([seed & 0xFFFFFFFF, zlib.crc32(key.encode())]))
 
 
+# the BatchNorm scales behind RepViT's residual branches (only keys under `.backbone.features.`: no en / mv / pf key contains that string)
+_RV_BRANCH_SCALES = ('channel_mixer.m.2.bn.weight', 'token_mixer.0.conv.bn.weight', 'token_mixer.0.conv1.bn.weight')
+
+
 def _is_norm_affine(key, sd):
     """A 1-D `bias` belongs to a BatchNorm / LayerNorm / GroupNorm iff its sibling `weight` is 1-D too
     (conv / linear weights on this path are all >= 2-D)."""
@@ -60,6 +64,8 @@ def condition_state_dict(sd, seed=0):
             v = U(-2.0, 2.0)
         elif leaf in ('cbias', 'sbias'):
             v = U(-1.0, 1.0)
+        elif leaf == 'weight' and ref.ndim == 1 and '.backbone.features.' in key and key.endswith(_RV_BRANCH_SCALES):
+            v = U(0.1, 0.3)                       # RepViT: 25 - 34 residual blocks in a row — with the generic scale every block adds a branch as large as its input
         elif leaf == 'weight' and ref.ndim == 1:
             v = U(0.5, 1.5)                       # norm scale
         elif leaf == 'bias' and _is_norm_affine(key, sd) and '_seg_head.' in key:

@@ -9,7 +9,7 @@ arithmetic operation a `torch.autograd.Function` from train_functional.py / trai
 kernels.  What torch does here is tensor plumbing: views, `cat` / `split` / channel shuffles, and the residual / bias additions, whose
 gradients autograd routes.  fp32 on GPU tensors only; there is no PyTorch-op or CPU fallback.
 
-Built for every family that has reference code: EdgeNeXt ('en') and MobileViT ('mv') backbones, Ghost-Dual-FPN ('gdf') and CSP-Dual-FPN
+Built for the EdgeNeXt ('en'), MobileViT ('mv') and RepViT ('rv') backbones (PoolFormer is inference only), Ghost-Dual-FPN ('gdf') and CSP-Dual-FPN
 ('cdf') necks, PointNet ('pn'), nano head.  PointNet++ (our own specification, no reference) raises NotImplementedError in training mode.
 """
 import math
@@ -40,8 +40,8 @@ _POS_TABLES = {}        # (H, W, device, hidden, temperature) -> the Fourier pos
 
 class TrainGraph:
     def __init__(self, model):
-        if model.backbone not in ('en', 'mv'):
-            raise NotImplementedError(f"training mode is not built for backbone={model.backbone!r} (inference only; 'en' and 'mv' train)")
+        if model.backbone not in ('en', 'mv', 'rv'):
+            raise NotImplementedError(f"training mode is not built for backbone={model.backbone!r} (inference only; 'en', 'mv' and 'rv' train)")
         self.m = model
         self.p = dict(model.named_parameters())
         self.b = dict(model.named_buffers())
@@ -265,6 +265,47 @@ class TrainGraph:
         x = self.mvit_block(self.mv2block(x, pfx + '.mv2.6', 2, ch[8]), pfx + '.mvit.2', 3)
         return [f2, f3, f4, self.conv_bn_silu(x, pfx + '.conv2')]
 
+    # ---------------------------------------------------------------------------------------------- RepViT
+    def conv2d_bn(self, x, pfx, stride=1, pad=0):
+        """Conv2d_BN (repvit.py:31-39): conv (no bias) + BatchNorm (1e-5)."""
+        return self.bn(TF.conv2d(x, self.P(pfx + '.c.weight'), None, stride, pad) if pad else TF.conv1x1(x, self.P(pfx + '.c.weight')), pfx + '.bn', 1e-5)
+
+    def repvit_block(self, x, pfx, stride, se):
+        """RepViTBlock (repvit.py:123-159), unfused: the three RepVGGDW branches and every BatchNorm on batch statistics.  The stride-2 depthwise 3x3 (pad 1) is the
+        stride-1 result at the even positions; the depthwise 1x1 is a per-channel scale."""
+        t = pfx + '.token_mixer'
+        if stride == 2:
+            d = TF.dwconv(x, self.P(t + '.0.c.weight'))[:, :, ::2, ::2].contiguous()
+            d = self.conv2d_bn(self.bn(d, t + '.0.bn', 1e-5), t + '.2')
+        else:
+            d = self.bn(TF.dwconv(x, self.P(t + '.0.conv.c.weight')), t + '.0.conv.bn', 1e-5)
+            d = d + self.bn(TF.channel_scale(x, self.P(t + '.0.conv1.c.weight').reshape(-1)), t + '.0.conv1.bn', 1e-5) + x
+            if se:                                       # timm SqueezeExcite: 1x1 convs with bias on the pooled vector
+                B, C = d.shape[0], d.shape[1]
+                g = TF.global_avg_pool(d).view(B, C, 1)
+                g = TF.act(TF.conv1x1(g, self.P(t + '.1.fc1.weight'), self.P(t + '.1.fc1.bias')), TF.ACT_RELU)
+                g = TF.act(TF.conv1x1(g, self.P(t + '.1.fc2.weight'), self.P(t + '.1.fc2.bias')), TF.ACT_SIGMOID)
+                d = TF.channel_scale(d, g.reshape(B, C))
+        c = pfx + '.channel_mixer.m'
+        return d + self.conv2d_bn(TF.act(self.conv2d_bn(d, c + '.0'), TF.ACT_GELU), c + '.2')
+
+    def repvit(self, x, pfx):
+        """RepViT.forward (repvit.py:244-251): the maps are features[out_slices], not the stage ends; the blocks behind the last one run without gradient — the
+        reference runs them in training mode too, so their running statistics and counters move while their parameters get no gradient."""
+        from .spec import REPVIT, repvit_rows
+        out = REPVIT[self.m.phi]['out']
+        x = self.conv2d_bn(TF.act(self.conv2d_bn(x, pfx + '.features.0.0', 2, 1), TF.ACT_GELU), pfx + '.features.0.2', 2, 1)
+        feats = []
+        for i, (inp, oup, stride, se) in enumerate(repvit_rows(self.m.phi), 1):
+            if i > out[-1]:
+                with torch.no_grad():
+                    x = self.repvit_block(x.detach(), f'{pfx}.features.{i}', stride, se)
+                continue
+            x = self.repvit_block(x, f'{pfx}.features.{i}', stride, se)
+            if i in out:
+                feats.append(x)
+        return feats
+
     # ---------------------------------------------------------------------------------------------- CSP neck blocks
     def base_conv_k(self, x, pfx, act, k=1):
         """BaseConv: conv k x k (pad (k-1)//2, no bias) + BN (1e-3) + activation (normal_conv.py:36-47)."""
@@ -299,7 +340,7 @@ class TrainGraph:
         """GhostDualFPN.forward (neck/ghostdualfpn.py:156-200)."""
         f = 'image_radar_encoder.fpn'
         w = self.w
-        m2, m3, m4, m5 = self.edgenext(x, f + '.backbone') if self.m.backbone == 'en' else self.mobilevit(x, f + '.backbone')
+        m2, m3, m4, m5 = {'en': self.edgenext, 'mv': self.mobilevit, 'rv': self.repvit}[self.m.backbone](x, f + '.backbone')
         csp = self.m.neck == 'cdf'                       # CSPDualFPN.forward (neck/cspdualfpn.py:193-237): the same graph with CSP blocks
         p5 = self.spp(m5, f + '.spp')
         c4 = torch.cat([self.upsample(p5, f + '.upsample_5_to_4'), m4], 1)

@@ -38,7 +38,8 @@ typedef struct ach_handle ach_handle;
 enum { ACH_DTYPE_F32 = 0, ACH_DTYPE_BF16 = 1,
        ACH_DTYPE_F16 = 2    /* fp16 activations and MFMA operands, fp32 accumulation: the type the reference's mixed-precision mode computes in
                              * (utils/utils_fit.py:120-121, train.py:37 --fp16).  Inputs / outputs are fp16, or bf16 with option "io_bf16" */ };
-enum { ACH_BACKBONE_EDGENEXT = 0, ACH_BACKBONE_MOBILEVIT = 1, ACH_BACKBONE_POOLFORMER = 2 };
+enum { ACH_BACKBONE_EDGENEXT = 0, ACH_BACKBONE_MOBILEVIT = 1, ACH_BACKBONE_POOLFORMER = 2,
+       ACH_BACKBONE_REPVIT = 4 /* 3 is reserved (the reference's default 'ef') and refused */ };
 enum { ACH_PHI_S0 = 0, ACH_PHI_S1 = 1, ACH_PHI_S2 = 2 };
 
 enum {
@@ -64,7 +65,7 @@ typedef struct ach_config {
     int32_t num_det;        /* detection classes           (Achelous.__init__ num_det)      */
     int32_t num_seg;        /* semantic classes            (num_seg)                        */
     int32_t phi;            /* ACH_PHI_*                   (phi)                            */
-    int32_t backbone;       /* ACH_BACKBONE_*              (backbone in {'en','mv','pf'})   */
+    int32_t backbone;       /* ACH_BACKBONE_*              (backbone in {'en','mv','pf','rv'}) */
     int32_t resolution;     /* square input size           (resolution)                     */
     int32_t pc_channels;    /* point features              (pc_channels)                    */
     int32_t pc_classes;     /* point classes               (pc_classes)                     */
