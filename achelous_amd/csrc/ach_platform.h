@@ -722,4 +722,8 @@ __device__ __forceinline__ unsigned xcd_block(unsigned w, unsigned n) { return (
 __host__ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ __forceinline__ long cdivl(long a, long b) { return (a + b - 1) / b; }
 
+// rows per workgroup of the kernels that own a band of rows of ONE sample and write per-band partials (k_poolformer.h's token mixer, k_repvit.h's depthwise conv):
+// by the map alone — the partials, and so a frame's result, must not depend on the batch
+inline int sample_band_rows(int H) { return H >= 64 ? 8 : (H >= 32 ? 4 : 2); }
+
 }  // namespace ach

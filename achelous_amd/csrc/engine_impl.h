@@ -113,14 +113,17 @@ public:
         else l.b.assign(size_t(l.N), 0.f);
         return l;
     }
-    void bn_coeffs(const std::string& pfx, double eps, std::vector<float>& scale, std::vector<float>& shift) const {
+    // BatchNorm as y = s x + t, in double: s = gamma / sqrt(var + eps), t = beta - mean s
+    void bn_coeffs_d(const std::string& pfx, double eps, std::vector<double>& s, std::vector<double>& t) const {
         const auto& g = W(pfx + ".weight").data; const auto& b = W(pfx + ".bias").data;
         const auto& m = W(pfx + ".running_mean").data; const auto& v = W(pfx + ".running_var").data;
-        scale.resize(g.size()); shift.resize(g.size());
-        for (size_t i = 0; i < g.size(); ++i) {
-            const double s = double(g[i]) / std::sqrt(double(v[i]) + eps);
-            scale[i] = float(s); shift[i] = float(double(b[i]) - double(m[i]) * s);
-        }
+        if (b.size() != g.size() || m.size() != g.size() || v.size() != g.size()) throw AchError{ACH_ERR_MISSING_KEY, "BatchNorm shapes at " + pfx};
+        s.resize(g.size()); t.resize(g.size());
+        for (size_t i = 0; i < g.size(); ++i) { s[i] = double(g[i]) / std::sqrt(double(v[i]) + eps); t[i] = double(b[i]) - double(m[i]) * s[i]; }
+    }
+    void bn_coeffs(const std::string& pfx, double eps, std::vector<float>& scale, std::vector<float>& shift) const {      // the same pair, rounded to float
+        std::vector<double> s, t; bn_coeffs_d(pfx, eps, s, t);
+        scale.assign(s.begin(), s.end()); shift.assign(t.begin(), t.end());
     }
     void fold_bn(Lin& l, const std::string& pfx, double eps) const {            // y = bn(Wx + b)
         std::vector<float> sc, sh; bn_coeffs(pfx, eps, sc, sh);
@@ -425,37 +428,27 @@ public:
     // neck: torch.cat((upsampled, backbone feature), 1) then needs no copy).  Consumed by the first block that produces an output.
     A preset_out; bool has_preset = false;
     A block_out(const A& like) {
-        if (has_preset) {
-            has_preset = false;
-            reached(kPtConcatSlice);            // (the neck on stream 2: the launch that writes this slice of the neck's concat buffer: the previous forward's neck, on stream 2, may still read it)
-            if (preset_out.B != like.B || preset_out.H != like.H || preset_out.W != like.W || preset_out.C != like.C)
-                throw AchError{ACH_ERR_INVALID, "preset block output does not match the block"};
-            return preset_out;
-        }
-        return alloc(like.B, like.H, like.W, like.C);
+        const A* dst = has_preset ? &preset_out : nullptr;
+        has_preset = false;
+        return out_like(like, dst, 1, "preset block output does not match the block");
     }
+    // a stage output shaped like `like`: the caller's destination `dst` (a slice of the neck's concat buffer, row pitch a multiple of `ld_mult` elements) when there
+    // is one, else a fresh allocation
+    A out_like(const A& like, const A* dst, long ld_mult, const char* mismatch) {
+        if (!dst) return alloc(like.B, like.H, like.W, like.C);
+        reached(kPtConcatSlice);                // (the neck on stream 2: the next launch writes this slice of the neck's concat buffer: the previous forward's neck, on stream 2, may still read it)
+        if (dst->B != like.B || dst->H != like.H || dst->W != like.W || dst->C != like.C || dst->ld % ld_mult != 0) throw AchError{ACH_ERR_INVALID, mismatch};
+        return *dst;
+    }
+    // four waves per tile (SPLIT) or one: the per-sample map size, not the batch, decides — a frame's result must not depend on the batch it is in
+    bool mlp_split_for(int HW) const { return mlp_split < 0 ? HW <= mlp_split_hw : mlp_split != 0; }
     bool fused_mlp_lin(const std::string& name, const std::string& pfx, const A& xin, const A& resid, int dw_ks, const Lin& l1, const Lin& l2,
                        int act, float ln_eps, A& y) {
         if (!fuse_mlp) return false;
         const int C = xin.C, DT = mlp_pick_dt(C);
         if (DT == 0 || (dw_ks != 0 && dw_ks != 3 && dw_ks != 5 && dw_ks != 7 && dw_ks != 9)) return false;
-        const int hidden = l1.N, k1 = cdiv(C, KC), J = cdiv(hidden, 32), hstep = 8 / VEC, ks2 = J * hstep;
+        const int hidden = l1.N, k1 = cdiv(C, KC);
         if (l1.K != C || l2.N != C || l2.K != hidden) throw AchError{ACH_ERR_MISSING_KEY, "MLP shapes at " + pfx};
-        std::vector<float> w1(size_t(J) * k1 * 2 * 64 * VEC, 0.f), b1(size_t(J) * 32, 0.f);
-        std::vector<float> w2(size_t(ks2) * DT * 64 * VEC, 0.f), b2(size_t(DT) * 16, 0.f);
-        if (!measuring) {
-            for (int n = 0; n < hidden; ++n) {
-                b1[n] = l1.b[n];
-                for (int k = 0; k < C; ++k) w1[size_t(wfrag_offset(n, k, 2, k1, VEC))] = l1.w[size_t(n) * C + k];
-            }
-            for (int n = 0; n < C; ++n) {
-                b2[n] = l2.b[n];
-                for (int kap = 0; kap < 32 * J; ++kap) {
-                    const int ch = mlp_hidden_channel(kap, VEC);
-                    if (ch < hidden) w2[size_t(wfrag_offset(n, kap, DT, ks2, VEC))] = l2.w[size_t(n) * hidden + ch];
-                }
-            }
-        }
         MlpParams mp;
         std::memset(&mp, 0, sizeof(mp));
         mp.X = xin.p; mp.ldx = xin.ld; mp.R = resid.p; mp.ldr = resid.ld;
@@ -476,10 +469,9 @@ public:
             for (int c = 0; c < C; ++c) { bt[c] = b[c]; for (int t = 0; t < kk; ++t) wt[size_t(t) * ldc + c] = w.data[size_t(c) * kk + t]; }
             mp.Wdw = up_f32(wt); mp.bdw = up_f32(bt);
         }
-        mp.W1 = up_T(w1); mp.b1 = up_f32(b1); mp.W2 = up_T(w2); mp.b2 = up_f32(b2);
-        mp.M = xin.rows(); mp.C = C; mp.k1 = k1; mp.J = J; mp.act = act; mp.ln_eps = ln_eps; mp.ln = 1; mp.Cout = C;
-        // per-sample map size, not batch, decides the geometry: a frame's result must not depend on the batch it is in
-        const bool split = mlp_split < 0 ? xin.H * xin.W <= mlp_split_hw : mlp_split != 0;
+        chain_weights(mp, C, DT, l1, act, l2);          // (behind the depthwise weights: the upload order is the plan's weight layout)
+        mp.M = xin.rows(); mp.ln_eps = ln_eps; mp.ln = 1;
+        const bool split = mlp_split_for(xin.H * xin.W);
         if (split && dw_ks && dw_even && mlp_even_dt(DT)) {               // the instantiated widths (launch_mlp)
             // deal the k1 * k tap rows to the four waves in contiguous shares when that lowers the slowest wave's count and no share spans
             // more than two k-steps (the exchange buffer holds two slots per wave)
@@ -543,7 +535,7 @@ public:
         if (!fuse_mlp) return false;
         const int Cin = x.C, hidden = l1.N, Cout = l2.N;
         const int k1 = cdiv(Cin, KC), J = cdiv(hidden, 32);
-        const bool split = allow_split && (mlp_split < 0 ? x.H * x.W <= mlp_split_hw : mlp_split != 0);
+        const bool split = allow_split && mlp_split_for(x.H * x.W);
         // narrow layers on maps that are not latency-bound: every weight fragment in registers, several tiles per wave (chain_kernel)
         const bool small = Cout <= 32 && k1 <= 3 && J <= 2 && !split;
         const int DT = small ? 2 : mlp_pick_dt(std::max(Cin, Cout));
@@ -1075,7 +1067,7 @@ public:
                 std::vector<float> a(static_cast<size_t>(C));
                 for (int c = 0; c < C; ++c) a[size_t(c)] = ls1[size_t(c)] * g1[size_t(c)];
                 A y = alloc(B, x.H, x.W, C);
-                const int RB = pf_mixer_band(x.H);
+                const int RB = sample_band_rows(x.H);
                 Mom my = alloc_mom(B, cdiv(x.H, RB));
                 {
                     PfMixParams mp{x.p, x.ld, y.p, y.ld, up_f32(a), mx.p, mx.P, my.p, x.H, x.W, C, RB, eps};
@@ -1094,8 +1086,7 @@ public:
                 std::memset(&q, 0, sizeof(q));
                 chain_weights(q.m, C, DT, l1, ACT_GELU, l2);
                 q.m.X = y.p; q.m.ldx = y.ld; q.m.Y = z.p; q.m.ldy = z.ld; q.m.M = y.rows();
-                // per-sample map size, not batch, decides the geometry (as for mlp_kernel): four waves per tile on the small maps
-                const bool split = mlp_split < 0 ? HW <= mlp_split_hw : mlp_split != 0;
+                const bool split = mlp_split_for(HW);
                 Mom mz = alloc_mom(B, pf_mlp_blocks(HW, split));
                 q.min = my.p; q.Pin = my.P; q.mout = mz.p; q.HW = HW; q.eps = eps; q.tpw = pf_mlp_tpw(HW, split);
                 add_op(bp + ".mlp", [q, DT, split, B](hipStream_t s) { launch_pf_mlp<T>(q, DT, split, B, s); },
@@ -1107,12 +1098,7 @@ public:
             const std::string n = pfx + ".norm" + std::to_string(2 * i);
             const auto& gw = W(n + ".weight").data; const auto& gb = W(n + ".bias").data;
             if (int(gw.size()) != C || int(gb.size()) != C) throw AchError{ACH_ERR_MISSING_KEY, "PoolFormer output norm width at " + n};
-            A out;
-            if (dst && dst[i]) {
-                out = *dst[i];
-                reached(kPtConcatSlice);        // (the next launch writes a slice of the neck's concat buffer)
-                if (out.B != x.B || out.H != x.H || out.W != x.W || out.C != C || out.ld % VEC != 0) throw AchError{ACH_ERR_INVALID, "PoolFormer output destination does not match the stage"};
-            } else out = alloc(B, x.H, x.W, C);
+            const A out = out_like(x, dst ? dst[i] : nullptr, VEC, "PoolFormer output destination does not match the stage");
             PfNormParams np{x.p, x.ld, out.p, out.ld, up_f32(gw), up_f32(gb), mx.p, mx.P, HW, C, eps};
             const dim3 grid(unsigned(cdiv(HW * (C / VEC), 256)), unsigned(B)), block(256);
             add_op(n, [np, grid, block](hipStream_t s) { ACH_LAUNCH(pf_norm_apply_kernel<T>, grid, block, s, np); }, 2.0 * double(x.rows()) * C * sizeof(T));
@@ -1122,14 +1108,6 @@ public:
     }
 
     // ------------------------------------------------------------------------------------------ RepViT (k_repvit.h)
-    // BatchNorm as y = s x + t, in double: s = gamma / sqrt(var + eps), t = beta - mean s
-    void bn_coeffs_d(const std::string& pfx, double eps, std::vector<double>& s, std::vector<double>& t) const {
-        const auto& g = W(pfx + ".weight").data; const auto& b = W(pfx + ".bias").data;
-        const auto& m = W(pfx + ".running_mean").data; const auto& v = W(pfx + ".running_var").data;
-        if (b.size() != g.size() || m.size() != g.size() || v.size() != g.size()) throw AchError{ACH_ERR_MISSING_KEY, "BatchNorm shapes at " + pfx};
-        s.resize(g.size()); t.resize(g.size());
-        for (size_t i = 0; i < g.size(); ++i) { s[i] = double(g[i]) / std::sqrt(double(v[i]) + eps); t[i] = double(b[i]) - double(m[i]) * s[i]; }
-    }
     // Conv2d_BN (repvit.py: conv without bias + BatchNorm2d, eps 1e-5) as one linear map: rows scaled by s, bias t.  `l` holds the conv's matrix (1x1 or implicit-GEMM layout)
     void fold_conv2d_bn(Lin& l, const std::string& pfx) const {
         std::vector<double> sc, sh; bn_coeffs_d(pfx + ".bn", 1e-5, sc, sh);
@@ -1207,7 +1185,7 @@ public:
                 rv_dw_weights(tm, inp, stride, wt, bs);
                 const int Ho = (x.H - 1) / stride + 1, Wo = (x.W - 1) / stride + 1, HW = Ho * Wo;
                 A d = alloc(B, Ho, Wo, inp);
-                RvDwParams dp{x.p, x.ld, d.p, d.ld, up_f32(wt), up_f32(bs), nullptr, x.H, x.W, Ho, Wo, inp, rv_dw_band(Ho)};
+                RvDwParams dp{x.p, x.ld, d.p, d.ld, up_f32(wt), up_f32(bs), nullptr, x.H, x.W, Ho, Wo, inp, sample_band_rows(Ho)};
                 const int P = cdiv(Ho, dp.RB);
                 if (se) dp.psum = alloc_f32(size_t(B) * P * inp);
                 add_op(tm + ".dw", [dp, stride, se, B](hipStream_t s) { launch_rv_dw3<T>(dp, stride, se, B, s); }, (double(x.rows()) + double(d.rows())) * inp * sizeof(T), 18.0 * double(d.rows()) * inp);
@@ -1240,19 +1218,13 @@ public:
                 const int DT = mlp_pick_dt(C);
                 if (DT == 0 || DT > 18 || l1.K != C || l2.N != C || l2.K != l1.N) throw AchError{ACH_ERR_UNSUPPORTED, "RepViT MLP shapes at " + bp};
                 const bool is_map = idx == kOut[ph][nmap];
-                A z;
-                if (is_map && dst && dst[nmap]) {
-                    z = *dst[nmap];
-                    reached(kPtConcatSlice);        // (the next launch writes a slice of the neck's concat buffer)
-                    if (z.B != d.B || z.H != d.H || z.W != d.W || z.C != C || z.ld % 8 != 0) throw AchError{ACH_ERR_INVALID, "RepViT output destination does not match the block"};
-                } else z = alloc(B, Ho, Wo, C);
+                const A z = out_like(d, is_map && dst ? dst[nmap] : nullptr, 8, "RepViT output destination does not match the block");      // (d is B x Ho x Wo x C here)
                 RvMlpParams q;
                 std::memset(&q, 0, sizeof(q));
                 chain_weights(q.m, C, DT, l1, ACT_GELU, l2);
                 q.m.X = d.p; q.m.ldx = d.ld; q.m.Y = z.p; q.m.ldy = z.ld; q.m.M = d.rows();
                 q.gate = gate; q.HW = HW;
-                // per-sample map size, not batch, decides the geometry (as for mlp_kernel): four waves per tile on the small maps
-                const bool split = mlp_split < 0 ? HW <= mlp_split_hw : mlp_split != 0;
+                const bool split = mlp_split_for(HW);
                 add_op(bp + ".mlp", [q, DT, split, B](hipStream_t s) { launch_rv_mlp<T>(q, DT, split, B, s); }, 2.0 * double(d.rows()) * C * sizeof(T), 4.0 * double(d.rows()) * C * l1.N);
                 tap("backbone.f" + std::to_string(idx), z);
                 x = z;

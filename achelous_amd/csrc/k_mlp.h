@@ -475,6 +475,11 @@ __global__ __launch_bounds__(256, (MlpOcc<DT, SPLIT, Store<T>::VEC>::blocks)) vo
     }
 }
 
+// f(integral_constant<int, dt>) for the dt of the list that equals DT; false when the width is not in the launcher's list (= not instantiated).
+// The width dispatch of launch_mlp, launch_pf_mlp (k_poolformer.h) and launch_rv_mlp (k_repvit.h), each with its own list.
+template <int... DTS, class F>
+inline bool mlp_for_dt(int DT, F f) { return ((DT == DTS ? (f(std::integral_constant<int, DTS>{}), true) : false) || ...); }
+
 template <class T>
 inline bool launch_mlp(const MlpParams& p, int DT, bool split, hipStream_t stream) {
     const long tiles = (p.M + 15) / 16;
@@ -482,11 +487,10 @@ inline bool launch_mlp(const MlpParams& p, int DT, bool split, hipStream_t strea
     // the even depthwise row split is instantiated where it pays: d = 144 (DT 10; EN-S2 stage 2, +0.7 % frames/s).  At d = 96 (DT 6, the
     // 80-register budget of six workgroups per CU) the variant spills 80 bytes and EN-S0 loses 0.8 %: not instantiated.
     if (split && p.dw_even && DT == 10) { ACH_LAUNCH((mlp_kernel<T, 10, true, true>), grid, block, stream, p); return true; }
-#define ACH_MLP_CASE(dt) \
-    if (DT == dt) { if (split) ACH_LAUNCH((mlp_kernel<T, dt, true>), grid, block, stream, p); else ACH_LAUNCH((mlp_kernel<T, dt, false>), grid, block, stream, p); return true; }
-    ACH_MLP_CASE(2) ACH_MLP_CASE(4) ACH_MLP_CASE(6) ACH_MLP_CASE(8) ACH_MLP_CASE(10) ACH_MLP_CASE(12) ACH_MLP_CASE(18) ACH_MLP_CASE(20)
-#undef ACH_MLP_CASE
-    return false;
+    return mlp_for_dt<2, 4, 6, 8, 10, 12, 18, 20>(DT, [&](auto dt) {
+        constexpr int D = decltype(dt)::value;
+        if (split) ACH_LAUNCH((mlp_kernel<T, D, true>), grid, block, stream, p); else ACH_LAUNCH((mlp_kernel<T, D, false>), grid, block, stream, p);
+    });
 }
 // ------------------------------------------------------------------------------------------ two tiles per wave (round 5)
 // The feed-forward blocks of MobileViT's transformers (LN -> fc1 -> SiLU -> fc2 -> + input; d = 144 / 192, hidden 2d) are plain-row launches of mlp_kernel with one

@@ -137,7 +137,6 @@ __global__ __launch_bounds__(256) void pf_norm_apply_kernel(const PfNormParams p
 // three neighbours (its own column and the two beside it, which the threads next to it fetch too: those come from L1), so a row of the
 // band is read from memory once; the two halo rows of a band are the only re-reads.  grid (cdiv(H, RB), B)
 struct PfMixParams { const void* X; long ldx; void* Y; long ldy; const float* a; const float* min; int Pin; float* mout; int H, W, C, RB; float eps; };
-inline int pf_mixer_band(int H) { return H >= 64 ? 8 : (H >= 32 ? 4 : 2); }        // by the map alone: the partials must not depend on the batch
 template <class T>
 __global__ __launch_bounds__(256) void pf_mixer_kernel(const PfMixParams p) { f16_sat_mode<T>();
     constexpr int VEC = Store<T>::VEC;
@@ -202,6 +201,9 @@ __global__ __launch_bounds__(256) void pf_mixer_kernel(const PfMixParams p) { f1
 // sample — so a tile's (mu, rstd) is one pair.  SPLIT = false: four tiles per workgroup, one per wave (grid.x = cdiv(tiles, 4)).  SPLIT = true (small
 // maps): the four waves share one tile, each takes every fourth hidden chunk, partial outputs summed through LDS in wave order (grid.x = tiles).
 // 16-bit k-chunks are two 16x16x16 instructions (mfma16_pair).
+// The chunk loop and the SPLIT reduction below are the same text as rv_mlp_kernel's (k_repvit.h) and, for the reduction, mlp_kernel's: a fix to one belongs in all
+// three.  Stated once as force-inlined helpers they compiled to other register allocations and more scratch in this kernel, so each kernel keeps its
+// own; the width dispatch (mlp_for_dt) and the weight packing are shared.
 struct PfMlpParams { MlpParams m; const float* min; int Pin; float* mout; int HW; float eps; int tpw; };
 // mlp_kernel's register budgets, except that the one-tile-per-wave kernels stop at five workgroups per CU: with the running moments next to the accumulators the
 // narrow widths spilled 12 / 20 bytes at six
@@ -333,11 +335,10 @@ inline int pf_mlp_blocks(int HW, bool split) { const int tiles = (HW + 15) / 16;
 template <class T>
 inline bool launch_pf_mlp(const PfMlpParams& q, int DT, bool split, int B, hipStream_t stream) {
     const dim3 grid(unsigned(pf_mlp_blocks(q.HW, split)), unsigned(B)), block(256);
-#define ACH_PFMLP_CASE(dt) \
-    if (DT == dt) { if (split) ACH_LAUNCH((pf_mlp_kernel<T, dt, true>), grid, block, stream, q); else ACH_LAUNCH((pf_mlp_kernel<T, dt, false>), grid, block, stream, q); return true; }
-    ACH_PFMLP_CASE(2) ACH_PFMLP_CASE(4) ACH_PFMLP_CASE(6) ACH_PFMLP_CASE(8) ACH_PFMLP_CASE(10) ACH_PFMLP_CASE(12) ACH_PFMLP_CASE(18)
-#undef ACH_PFMLP_CASE
-    return false;
+    return mlp_for_dt<2, 4, 6, 8, 10, 12, 18>(DT, [&](auto dt) {
+        constexpr int D = decltype(dt)::value;
+        if (split) ACH_LAUNCH((pf_mlp_kernel<T, D, true>), grid, block, stream, q); else ACH_LAUNCH((pf_mlp_kernel<T, D, false>), grid, block, stream, q);
+    });
 }
 
 // ------------------------------------------------------------------------------------------ stem

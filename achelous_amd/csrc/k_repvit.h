@@ -70,7 +70,6 @@ __global__ __launch_bounds__(256) void rv_stem_kernel(const RvStemParams p) { f1
 // are the only re-reads.  An output row's sum is always taken in the order (row above, own row, row below), whatever the band: bit-identical for any band height.
 // SE: the workgroup's per-channel sum of the values as stored goes to psum[(sample * bands + band) * C + c].        grid (cdiv(Ho, RB), B)
 struct RvDwParams { const void* X; long ldx; void* Y; long ldy; const float* w; const float* bias; float* psum; int H, W, Ho, Wo, C, RB; };
-inline int rv_dw_band(int Ho) { return Ho >= 64 ? 8 : (Ho >= 32 ? 4 : 2); }          // by the map alone: the partials must not depend on the batch
 template <class T, int STRIDE, bool SE>
 __global__ __launch_bounds__(256) void rv_dw3_kernel(const RvDwParams p) { f16_sat_mode<T>();
     constexpr int VEC = Store<T>::VEC;
@@ -217,6 +216,9 @@ __global__ __launch_bounds__(256) void rv_gate_kernel(const RvGateParams p) {
 // gate vector.  SPLIT = false: four tiles per workgroup, one per wave (grid.x = cdiv(tiles, 4)).  SPLIT = true (small maps): the four waves share one tile,
 // each takes every fourth hidden chunk, partial outputs summed through LDS in wave order (grid.x = tiles).  16-bit k-chunks are two 16x16x16 instructions
 // (mfma16_pair).
+// The chunk loop and the SPLIT reduction below are the same text as pf_mlp_kernel's (k_poolformer.h) and, for the reduction, mlp_kernel's: a fix to one belongs in
+// all three.  Stated once as force-inlined helpers they compiled to other register allocations in this kernel, so each kernel keeps its own; the
+// width dispatch (mlp_for_dt) and the weight packing are shared.
 struct RvMlpParams { MlpParams m; const float* gate; int HW; };
 template <class T, int DT, bool SPLIT>
 __global__ __launch_bounds__(256, (MlpOcc<DT, SPLIT, Store<T>::VEC>::blocks)) void rv_mlp_kernel(const RvMlpParams q) { f16_sat_mode<T>();
@@ -338,11 +340,10 @@ inline int rv_mlp_blocks(int HW, bool split) { const int tiles = (HW + 15) / 16;
 template <class T>
 inline bool launch_rv_mlp(const RvMlpParams& q, int DT, bool split, int B, hipStream_t stream) {
     const dim3 grid(unsigned(rv_mlp_blocks(q.HW, split)), unsigned(B)), block(256);
-#define ACH_RVMLP_CASE(dt) \
-    if (DT == dt) { if (split) ACH_LAUNCH((rv_mlp_kernel<T, dt, true>), grid, block, stream, q); else ACH_LAUNCH((rv_mlp_kernel<T, dt, false>), grid, block, stream, q); return true; }
-    ACH_RVMLP_CASE(2) ACH_RVMLP_CASE(4) ACH_RVMLP_CASE(6) ACH_RVMLP_CASE(8) ACH_RVMLP_CASE(10) ACH_RVMLP_CASE(12) ACH_RVMLP_CASE(18)
-#undef ACH_RVMLP_CASE
-    return false;
+    return mlp_for_dt<2, 4, 6, 8, 10, 12, 18>(DT, [&](auto dt) {
+        constexpr int D = decltype(dt)::value;
+        if (split) ACH_LAUNCH((rv_mlp_kernel<T, D, true>), grid, block, stream, q); else ACH_LAUNCH((rv_mlp_kernel<T, D, false>), grid, block, stream, q);
+    });
 }
 
 }  // namespace ach
