@@ -1,7 +1,7 @@
 """The one place where the training, data and serving modules meet ctypes for the STATELESS entries of the C ABI (include/achelous.h: `ach_train_*`, `ach_eval_*`,
 `ach_data_*`, the resample pass) and for the engine handle that serves the stateless pre / post-processing kernels.  Nothing here knows a model: library choice
 with its one test hook, the return-code check, tensor -> pointer / stream, and the GEMM call forms with their strides read from the tensors.
-(`engine.py` binds the library and owns `NativeEngine`; this module is what sits between it and train_ops / train_functional / losses / metrics / data / prepost.)
+(`engine.py` binds the library and owns `NativeEngine`; this module is what sits between it and train_functional / losses / metrics / data / prepost.)
 """
 import ctypes
 

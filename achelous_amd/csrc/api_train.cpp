@@ -136,21 +136,6 @@ int ach_train_bn_relu_bwd(const float* z, const float* y, const float* dy, const
     });
 }
 
-int ach_train_dw3x3(const float* x, const float* w, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t flip, void* stream) {
-    return stateless(stream, [&](hipStream_t st) {
-        if (!x || !w || !y || B <= 0 || C <= 0 || H <= 0 || W <= 0) throw ach::AchError{ACH_ERR_INVALID, "bad train_dw3x3 arguments"};
-        ach::DwTrainParams p{x, w, y, B, C, H, W, flip};
-        ACH_TRAIN_1D(ach::train_dw3x3_kernel, p, long(B) * C * H * W);
-    });
-}
-int ach_train_dw3x3_wgrad(const float* x, const float* dz, float* dw, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    return stateless(stream, [&](hipStream_t st) {
-        if (!x || !dz || !dw || B <= 0 || C <= 0 || H <= 0 || W <= 0) throw ach::AchError{ACH_ERR_INVALID, "bad train_dw3x3_wgrad arguments"};
-        ach::DwWgradParams p{x, dz, dw, B, C, H, W};
-        ACH_TRAIN_ROWS(ach::train_dw3x3_wgrad_kernel, p, C);
-    });
-}
-
 int ach_train_max_points(const float* x, float* y, int32_t* idx, const float* dy, float* dx, int64_t rows, int32_t N, void* stream) {
     return stateless(stream, [&](hipStream_t st) {                                 /* forward when dy == NULL, backward otherwise */
         if (rows <= 0 || N <= 0 || !idx) throw ach::AchError{ACH_ERR_INVALID, "bad train_max_points arguments"};

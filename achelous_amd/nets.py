@@ -341,15 +341,15 @@ class Achelous(nn.Module):
         """Training mode (train.py:400-420, utils/utils_fit.py:37-166): the unfused fp32 statement of the network on native forward /
         backward kernels (train_graph.py) — BatchNorm with batch statistics and running-estimate updates, gradients for every parameter
         through autograd.  Same output structure as the inference path; the outputs carry `grad_fn`."""
-        from . import train_graph, train_ops
+        from . import _native, train_graph, train_functional as TF
         has_pts = self.pc_seg_kind != 'none'
-        if not (x.is_cuda and x_radar.is_cuda and (not has_pts or x_point_clouds.is_cuda)) and not getattr(train_ops._lib, 'test_library', None):
+        if not (x.is_cuda and x_radar.is_cuda and (not has_pts or x_point_clouds.is_cuda)) and not getattr(_native.lib, 'test_library', None):
             raise RuntimeError("achelous_amd.Achelous.forward needs GPU tensors (HIP training kernels; there is no CPU path)")
         B = self._check_inputs(x, x_radar, x_point_clouds)
         precision = getattr(self, 'train_precision', 'fp32')          # (modules pickled before round 5 have no such attribute: utils_fit.py:378 pickles the module)
         if precision not in ('fp32', 'bf16'):
             raise ValueError(f"train_precision must be 'fp32' or 'bf16', got {precision!r}")
-        train_ops.set_gemm_precision(x, 1 if precision == 'bf16' else 0)
+        TF.set_gemm_precision(x, 1 if precision == 'bf16' else 0)
         det, se, lane, pc = train_graph.TrainGraph(self).forward(x, x_radar, x_point_clouds if has_pts else None)
         return (list(det), se, lane, pc) if has_pts else (list(det), se, lane)
 

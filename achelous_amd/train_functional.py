@@ -2,6 +2,7 @@
 
 Each function below is a `torch.autograd.Function` whose forward AND backward are hand-written HIP kernels; PyTorch supplies tensors,
 streams and the autograd tape only (views, `cat`, slices and residual adds between them are routed by autograd).  fp32, contiguous NCHW.
+This is the one home of the autograd primitives (the shared MLP and the PointNet glue included) and of `set_gemm_precision`.
 `achelous_amd/train_graph.py` composes them into `Achelous.forward` for `.train()` (the reference runs the same
 arithmetic through ATen autograd, utils/utils_fit.py:37-166).  No PyTorch-op or CPU fallback: without the HIP library these raise.
 """
@@ -11,9 +12,53 @@ import torch
 
 from ._native import NULL as _NULL, lib as _lib, check as _check, ptr as _p, stream as _stream, f32c as _f32, empty as _empty, prec as _prec
 from ._native import gemm_batched, gemm_dw, gemm_w_cols, gemm_wt_dz
-from .train_ops import _bn_train_fwd, _bn_train_bwd, _LinearFn
 
 ACT_RELU, ACT_SILU, ACT_GELU, ACT_SIGMOID = 0, 1, 2, 3
+
+
+def set_gemm_precision(t, precision):
+    """Operand type of every training GEMM from now on, process-wide: 0 = fp32 MFMA, 1 = operands rounded to bf16 while staged, fp32
+    accumulation (include/achelous.h).  `t`: any tensor of the device the step runs on (selects the library as `_lib` does).  Returns the previous value."""
+    L = _lib(t).lib
+    prev = L.ach_train_get_gemm_precision()
+    if L.ach_train_set_gemm_precision(int(precision)) != 0:
+        raise ValueError(f"gemm precision must be 0 (fp32) or 1 (bf16 operands), got {precision!r}")
+    return prev
+
+
+def _update_running(lib, s, mean, var, running_mean, running_var, momentum, m):
+    """nn.BatchNorm's running-estimate update as ONE native launch (it was four element-wise torch launches per layer)."""
+    if running_mean.dtype != torch.float32 or running_var.dtype != torch.float32 or not running_mean.is_contiguous() or not running_var.is_contiguous():
+        raise TypeError("BatchNorm running statistics must be contiguous float32 tensors")
+    _check(lib, lib.lib.ach_train_bn_running(_p(mean), _p(var), _p(running_mean), _p(running_var), mean.numel(), float(momentum), float(m) / float(max(m - 1, 1)), s))
+
+
+def _bn_train_fwd(lib, s, z3, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
+    """Shared tail of the conv + BatchNorm [+ ReLU] Functions on z3 [B, C, N]: statistics, running update (nn.BatchNorm: running <- (1 - m) running + m batch,
+    unbiased variance), normalise."""
+    B, C, N = z3.shape
+    mean = torch.empty(C, dtype=torch.float32, device=z3.device)
+    var = torch.empty(C, dtype=torch.float32, device=z3.device)
+    if training:
+        _check(lib, lib.lib.ach_train_bn_stats(_p(z3), _p(mean), _p(var), B, C, N, s))
+        if running_mean is not None:
+            _update_running(lib, s, mean, var, running_mean, running_var, momentum, B * N)
+    else:
+        mean.copy_(running_mean)
+        var.copy_(running_var)
+    y = torch.empty_like(z3)
+    _check(lib, lib.lib.ach_train_bn_relu_fwd(_p(z3), _p(mean), _p(var), _p(gamma), _p(beta), _p(y), B, C, N, float(eps), int(relu), s))
+    return y, mean, var
+
+
+def _bn_train_bwd(lib, s, z3, y, dy, mean, var, gamma, eps, relu):
+    """Backward of `_bn_train_fwd` in training mode on z3 [B, C, N] (dy contiguous) -> (dz, dgamma, dbeta)"""
+    B, C, N = z3.shape
+    dgamma = torch.empty(C, dtype=torch.float32, device=z3.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=z3.device)
+    dz = torch.empty_like(z3)
+    _check(lib, lib.lib.ach_train_bn_relu_bwd(_p(z3), _p(y), _p(dy), _p(mean), _p(var), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), B, C, N, eps, relu, s))
+    return dz, dgamma, dbeta
 
 
 def _bias_grad(lib, s, dy, B, C, n):
@@ -448,6 +493,186 @@ def bmm_nt(a, b):
 
 def bmm_nn(a, b):
     return _BmmFn.apply(a, b, False)
+
+
+# ------------------------------------------------------------------------------------------------------------------ PointNet: shared MLP, linear over columns, per-sample transform, max over points, log-softmax
+class _SharedMLP1dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
+        for t in (x, weight, gamma, beta):
+            if t.dtype != torch.float32:
+                raise TypeError("SharedMLP1d trains in float32")
+        x = x.contiguous()
+        B, cin, N = x.shape
+        cout = weight.shape[0]
+        w2 = weight.detach().reshape(cout, cin).contiguous()
+        lib = _lib(x)
+        s = _stream(x)
+        z = torch.empty(B, cout, N, dtype=torch.float32, device=x.device)
+        bs = bias.detach().contiguous() if bias is not None else None           # bound to a name: a temporary would be freed before the kernel reads it
+        ctx.prec = _prec(lib)
+        gemm_w_cols(lib, s, w2, x, z, bs, ctx.prec)
+        g = gamma.detach().contiguous()
+        y, mean, var = _bn_train_fwd(lib, s, z, g, beta.detach().contiguous(), running_mean, running_var, training, momentum, eps, relu)
+        ctx.save_for_backward(x, w2, z, y, mean, var, g)
+        ctx.cfg = (training, float(eps), int(relu), bias is not None, tuple(weight.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2, z, y, mean, var, gamma = ctx.saved_tensors
+        training, eps, relu, has_bias, wshape = ctx.cfg
+        if not training:
+            raise NotImplementedError("SharedMLP1d backward is built for training mode (batch statistics)")
+        lib = _lib(x)
+        s = _stream(x)
+        dz, dgamma, dbeta = _bn_train_bwd(lib, s, z, y, dy.contiguous(), mean, var, gamma, eps, relu)
+        dx = torch.empty_like(x)
+        gemm_wt_dz(lib, s, w2, dz, dx, ctx.prec)
+        dw = torch.empty(wshape, dtype=torch.float32, device=x.device)          # in the parameter's own shape (a VIEW of a 2-D buffer would make AccumulateGrad clone it: one copy per parameter and step)
+        gemm_dw(lib, s, dz, x, dw, ctx.prec)
+        # a bias in front of a training-mode BatchNorm has zero gradient: the batch mean it shifts is subtracted again (sum dz = 0)
+        dbias = torch.zeros(w2.shape[0], dtype=torch.float32, device=x.device) if has_bias else None
+        return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None
+
+
+def shared_mlp(x, weight, bias, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, relu=True):
+    """Conv1d(k = 1) / Linear + BatchNorm1d [+ ReLU] on x [B, Cin, N] as ONE autograd node (pointnet_utils.py:29-31, 69-71, 124-127)."""
+    return _SharedMLP1dFn.apply(x, weight, bias, gamma, beta, running_mean, running_var, training, momentum, eps, relu)
+
+
+class _LinearFn(torch.autograd.Function):
+    """z = W x + b on [B, Cin, N] (a Conv1d of kernel 1 / a Linear with N = 1) without normalisation: fc3 of the STNs, conv4 of the head."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        B, cin, N = x.shape
+        cout = weight.shape[0]
+        w2 = weight.detach().reshape(cout, cin).contiguous()
+        lib = _lib(x)
+        z = torch.empty(B, cout, N, dtype=torch.float32, device=x.device)
+        bs = bias.detach().contiguous() if bias is not None else None           # bound to a name: a temporary would be freed before the kernel reads it
+        ctx.prec = _prec(lib)
+        gemm_w_cols(lib, _stream(x), w2, x, z, bs, ctx.prec)
+        ctx.save_for_backward(x, w2)
+        ctx.cfg = (bias is not None, tuple(weight.shape))
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, w2 = ctx.saved_tensors
+        has_bias, wshape = ctx.cfg
+        B, cout, N = dz.shape
+        lib = _lib(x)
+        L, s = lib.lib, _stream(x)
+        dz = dz.contiguous()
+        dx = torch.empty_like(x)
+        gemm_wt_dz(lib, s, w2, dz, dx, ctx.prec)
+        dw = torch.empty(wshape, dtype=torch.float32, device=x.device)          # (in the parameter's own shape: a VIEW of a 2-D buffer would make autograd's AccumulateGrad clone it — one copy per parameter and step)
+        gemm_dw(lib, s, dz, x, dw, ctx.prec)
+        db = None
+        if has_bias:                      # db[c] = sum over (B, N) of dz = B N x the per-channel mean the statistics kernel returns
+            db = torch.empty(cout, dtype=torch.float32, device=x.device)
+            scratch = torch.empty(cout, dtype=torch.float32, device=x.device)
+            _check(lib, L.ach_train_bn_stats(_p(dz), _p(db), _p(scratch), B, cout, N, s))
+            db = db * float(B * N)
+        return dx, dw, db
+
+
+class _BmmPointsFn(torch.autograd.Function):
+    """y[b] = T[b]^T x[b]  for x [B, K, N], T [B, K, K]  — `torch.bmm(x.transpose(2, 1), trans).transpose(2, 1)` (pointnet_utils.py:110, 118-120)."""
+
+    @staticmethod
+    def forward(ctx, x, T):
+        x, T = x.contiguous(), T.contiguous()
+        lib = _lib(x)
+        y = torch.empty_like(x)
+        ctx.prec = _prec(lib)
+        gemm_batched(lib, _stream(x), T, x, y, True, False, ctx.prec)
+        ctx.save_for_backward(x, T)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, T = ctx.saved_tensors
+        lib = _lib(x)
+        s = _stream(x)
+        dy = dy.contiguous()
+        dx, dT = torch.empty_like(x), torch.empty_like(T)
+        gemm_batched(lib, s, T, dy, dx, False, False, ctx.prec)              # dx[b] = T[b] dy[b]
+        gemm_batched(lib, s, x, dy, dT, False, True, ctx.prec)               # dT[b] = x[b] dy[b]^T
+        return dx, dT
+
+
+class _MaxPointsFn(torch.autograd.Function):
+    """[B, C, N] -> [B, C]: `torch.max(x, 2)[0]` with the arg-max kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        B, C, N = x.shape
+        lib = _lib(x)
+        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        idx = torch.empty(B, C, dtype=torch.int32, device=x.device)
+        _check(lib, lib.lib.ach_train_max_points(_p(x), _p(y), _p(idx), _NULL, _NULL, B * C, N, _stream(x)))
+        ctx.save_for_backward(idx)
+        ctx.shape = (B, C, N)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        B, C, N = ctx.shape
+        lib = _lib(dy)
+        dy = dy.contiguous()
+        dx = torch.empty(B, C, N, dtype=torch.float32, device=dy.device)
+        _check(lib, lib.lib.ach_train_max_points(_NULL, _NULL, _p(idx), _p(dy), _p(dx), B * C, N, _stream(dy)))
+        return dx
+
+
+class _LogSoftmaxPointsFn(torch.autograd.Function):
+    """z [B, K, N] -> log_softmax over K written as [B, N, K] (pointnet_sem_seg.py:34-37)."""
+
+    @staticmethod
+    def forward(ctx, z):
+        z = z.contiguous()
+        B, K, N = z.shape
+        lib = _lib(z)
+        y = torch.empty(B, N, K, dtype=torch.float32, device=z.device)
+        _check(lib, lib.lib.ach_train_log_softmax(_p(z), _p(y), _NULL, _NULL, B, K, N, _stream(z)))
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        B, N, K = y.shape
+        lib = _lib(y)
+        dy = dy.contiguous()
+        dz = torch.empty(B, K, N, dtype=torch.float32, device=y.device)
+        _check(lib, lib.lib.ach_train_log_softmax(_NULL, _p(y), _p(dy), _p(dz), B, K, N, _stream(y)))
+        return dz
+
+
+def linear_cols(x, weight, bias=None):
+    """z = W x + b over the channels of x [B, Cin, N]; weight [Co, Cin] or [Co, Cin, 1]."""
+    return _LinearFn.apply(x, weight, bias)
+
+
+def bmm_points(x, T):
+    """y[b] = T[b]^T x[b] for x [B, K, N], T [B, K, K]."""
+    return _BmmPointsFn.apply(x, T)
+
+
+def max_points(x):
+    """[B, C, N] -> [B, C], the maximum over the points."""
+    return _MaxPointsFn.apply(x)
+
+
+def log_softmax_points(z):
+    """z [B, K, N] -> log-probabilities [B, N, K]."""
+    return _LogSoftmaxPointsFn.apply(z)
 
 
 # ------------------------------------------------------------------------------------------------------------------ resampling / pooling

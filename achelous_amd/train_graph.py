@@ -5,7 +5,7 @@ Training mode differs from the inference path in one respect that matters — Ba
 running estimates (DropPath / Dropout are built with rate 0: edgenext_modules/model.py:14-30, sdta_encoder.py:10-11) — and that is
 exactly what the inference engine cannot do, because it folds the running statistics into the convolutions.  So this is a second,
 unfused statement of the same network: a functional evaluator over the module's parameter tree (reference state-dict keys), every
-arithmetic operation a `torch.autograd.Function` from train_functional.py / train_ops.py whose forward and backward are hand-written HIP
+arithmetic operation a `torch.autograd.Function` from train_functional.py whose forward and backward are hand-written HIP
 kernels.  What torch does here is tensor plumbing: views, `cat` / `split` / channel shuffles, and the residual / bias additions, whose
 gradients autograd routes.  fp32 on GPU tensors only; there is no PyTorch-op or CPU fallback.
 
@@ -17,36 +17,30 @@ import math
 import torch
 
 from . import train_functional as TF
-from .train_ops import _SharedMLP1dFn, _LinearFn, _BmmPointsFn, _MaxPointsFn, _LogSoftmaxPointsFn
+from .spec import EDGENEXT, WIDTHS, MOBILEVIT
 
-EDGENEXT = {  # edgenext_modules/model.py:14-66: depths, widths, heads, SDTA scales, depthwise kernel per stage
-    'S0': dict(depths=[2, 2, 6, 2], heads=4, scales=[2, 2, 3, 4], ks=[3, 5, 7, 9]),
-    'S1': dict(depths=[3, 3, 9, 3], heads=4, scales=[2, 2, 3, 4], ks=[3, 5, 7, 9]),
-    'S2': dict(depths=[3, 3, 9, 3], heads=8, scales=[2, 2, 3, 4], ks=[3, 5, 7, 9]),
-}
-WIDTHS = {'S0': [32, 48, 96, 176], 'S1': [32, 48, 120, 224], 'S2': [32, 64, 144, 288]}        # neck/ghostdualfpn.py:20-25
 BN_MOMENTUM = 0.1
-
-
-MOBILEVIT = {  # backbone/vision/mobilevit_modules/mobilevit.py:225-240: channel plan (transformer widths are read from the weights)
-    'S0': [16, 16, 32, 32, 48, 48, 96, 96, 96, 96, 176],
-    'S1': [16, 32, 32, 32, 48, 48, 120, 120, 120, 120, 224],
-    'S2': [16, 32, 32, 32, 64, 64, 144, 144, 144, 144, 288],
-}
 
 
 _POS_TABLES = {}        # (H, W, device, hidden, temperature) -> the Fourier position table [1, 64, H, W]
 
 
-class TrainGraph:
-    def __init__(self, model):
-        if model.backbone not in ('en', 'mv', 'rv'):
-            raise NotImplementedError(f"training mode is not built for backbone={model.backbone!r} (inference only; 'en', 'mv' and 'rv' train)")
-        self.m = model
-        self.p = dict(model.named_parameters())
-        self.b = dict(model.named_buffers())
-        self.cfg = EDGENEXT[model.phi]
-        self.w = WIDTHS[model.phi]
+def _dot(pfx):
+    """the key prefix of a submodule: 'pfx.' — or '' for the module the evaluator was built over"""
+    return pfx + '.' if pfx else ''
+
+
+class Layers:
+    """The layers every part of the network is made of, evaluated over the parameters and buffers of ANY `nn.Module` with the reference's state-dict keys: the model
+    (`TrainGraph` below adds its wiring) or a stand-alone block of train_ops.py, whose `forward` is one call here.  `training`: batch statistics, running estimates and
+    `num_batches_tracked` updated as nn.BatchNorm does — or, False, the running statistics (forward only, as the Functions' backward is built for batch statistics).
+    The BatchNorm constants are stated HERE, per layer kind, not read from the module: eps 1e-5 / momentum 0.1 (torch's defaults, with which the Ghost and PointNet
+    layers — and the stand-alone blocks — are built) and eps 1e-3 / momentum 0.03 (BaseConv, SPP); a value poked into a block's `module.bn` afterwards is not seen."""
+
+    def __init__(self, module, training=True):
+        self.training = training
+        self.p = dict(module.named_parameters())
+        self.b = dict(module.named_buffers())
         self._nbt = []                    # the num_batches_tracked buffers of the BatchNorm layers this forward went through: incremented together at its end (one multi-tensor launch, not 80)
 
     # ---------------------------------------------------------------------------------------------- parameter access, layers
@@ -57,11 +51,12 @@ class TrainGraph:
         return key in self.p
 
     def bn(self, x, pfx, eps, relu=False):
-        """nn.BatchNorm in training mode: batch statistics, running estimates and num_batches_tracked updated.  The BaseConv / SPP Conv
+        """nn.BatchNorm: in training mode batch statistics, running estimates and num_batches_tracked updated.  The BaseConv / SPP Conv
         layers are built with eps 1e-3 AND momentum 0.03 (normal_conv.py:45, spp.py:31); every other BatchNorm has torch's defaults."""
-        self._nbt.append(self.b[pfx + '.num_batches_tracked'])
+        if self.training:
+            self._nbt.append(self.b[pfx + '.num_batches_tracked'])
         return TF.batchnorm(x, self.P(pfx + '.weight'), self.P(pfx + '.bias'), self.b[pfx + '.running_mean'], self.b[pfx + '.running_var'],
-                            True, 0.03 if eps == 1e-3 else BN_MOMENTUM, eps, relu)
+                            self.training, 0.03 if eps == 1e-3 else BN_MOMENTUM, eps, relu)
 
     def conv(self, x, pfx, stride=1, pad=0, depthwise=False):
         w = self.P(pfx + '.weight')
@@ -92,15 +87,81 @@ class TrainGraph:
 
     def ghost(self, x, pfx, oup, relu=True):
         """GhostModule (backbone/conv_utils/ghost_conv.py:6-29)."""
-        x1 = self.bn(self.conv(x, pfx + '.primary_conv.0'), pfx + '.primary_conv.1', 1e-5, relu)
-        x2 = self.bn(self.conv(x1, pfx + '.cheap_operation.0', depthwise=True), pfx + '.cheap_operation.1', 1e-5, relu)
+        p = _dot(pfx)
+        x1 = self.bn(self.conv(x, p + 'primary_conv.0'), p + 'primary_conv.1', 1e-5, relu)
+        x2 = self.bn(self.conv(x1, p + 'cheap_operation.0', depthwise=True), p + 'cheap_operation.1', 1e-5, relu)
         return torch.cat([x1, x2], 1)[:, :oup]
 
-    def ghost_bottleneck(self, x, pfx, out_chs):
-        """GhostBottleneck, stride 1, in != out (ghost_conv.py:32-70)."""
-        y = self.ghost(self.ghost(x, pfx + '.ghost1', x.shape[1], True), pfx + '.ghost2', out_chs, False)
-        s = self.bn(self.conv(x, pfx + '.shortcut.0', depthwise=True), pfx + '.shortcut.1', 1e-5)
-        return y + self.bn(self.conv(s, pfx + '.shortcut.2'), pfx + '.shortcut.3', 1e-5)
+    def ghost_bottleneck(self, x, pfx, out_chs, mid=None):
+        """GhostBottleneck, stride 1 (ghost_conv.py:32-70); `mid` defaults to the input width (the neck's); in == out: the shortcut is the identity."""
+        p = _dot(pfx)
+        y = self.ghost(self.ghost(x, p + 'ghost1', mid or x.shape[1], True), p + 'ghost2', out_chs, False)
+        if x.shape[1] == out_chs:
+            return y + x
+        s = self.bn(self.conv(x, p + 'shortcut.0', depthwise=True), p + 'shortcut.1', 1e-5)
+        return y + self.bn(self.conv(s, p + 'shortcut.2'), p + 'shortcut.3', 1e-5)
+
+    # ---------------------------------------------------------------------------------------------- PointNet
+    def shared_mlp(self, x, conv, bn, relu=True):
+        """Conv1d(k=1) / Linear + BatchNorm1d [+ ReLU] on [B, C, N] (pointnet_utils.py:29-31, 69-71, 124-127)."""
+        if self.training:
+            self._nbt.append(self.b[bn + '.num_batches_tracked'])
+        return TF.shared_mlp(x, self.P(conv + '.weight'), self.P(conv + '.bias'), self.P(bn + '.weight'), self.P(bn + '.bias'),
+                             self.b[bn + '.running_mean'], self.b[bn + '.running_var'], self.training, BN_MOMENTUM, 1e-5, relu)
+
+    def fc_bn(self, x, fc, bn):
+        """Linear + BatchNorm1d + ReLU on [B, C]: the batch is the axis of the statistics, i.e. the shared MLP on [1, C, B]."""
+        return self.shared_mlp(x.t().contiguous().unsqueeze(0), fc, bn).squeeze(0).t()
+
+    def rows_mlp(self, rows, conv, bn):
+        """Conv (k = 1) + BatchNorm + ReLU over ROWS [R, C]: the statistics run over all rows — BatchNorm2d over (B, centroids, samples) of a set-abstraction level,
+        BatchNorm1d over (B, points) of a propagation level — i.e. the shared MLP on [1, C, R]."""
+        return self.shared_mlp(rows.t().contiguous().unsqueeze(0), conv, bn).squeeze(0).t().contiguous()
+
+    def stn(self, x, pfx, k):
+        """STN3d / STNkd (pointnet_utils.py:10-85)."""
+        y = self.shared_mlp(x, pfx + '.conv1', pfx + '.bn1')
+        y = self.shared_mlp(y, pfx + '.conv2', pfx + '.bn2')
+        y = TF.max_points(self.shared_mlp(y, pfx + '.conv3', pfx + '.bn3'))
+        y = self.fc_bn(self.fc_bn(y, pfx + '.fc1', pfx + '.bn4'), pfx + '.fc2', pfx + '.bn5')
+        y = TF.linear_cols(y.t().contiguous().unsqueeze(0), self.P(pfx + '.fc3.weight'), self.P(pfx + '.fc3.bias')).squeeze(0).t()
+        return (y + torch.eye(k, dtype=y.dtype, device=y.device).reshape(1, k * k)).view(-1, k, k)
+
+    def pointnet(self, pts, pfx='pc_seg_model'):
+        """PointNet_SEG.forward / PointNetEncoder.forward (pointnet_sem_seg.py:26-37, pointnet_utils.py:103-133): pts [B, channels, N] -> log-probabilities [B, N, classes]."""
+        p = _dot(pfx)
+        B, D, N = pts.shape
+        trans = self.stn(pts, p + 'feat.stn', 3)
+        xyz = TF.bmm_points(pts[:, :3].contiguous(), trans)                   # only x, y, z are transformed; the other features pass through
+        x = torch.cat([xyz, pts[:, 3:]], 1) if D > 3 else xyz
+        x = self.shared_mlp(x, p + 'feat.conv1', p + 'feat.bn1')
+        x = TF.bmm_points(x, self.stn(x, p + 'feat.fstn', 32))
+        pointfeat = x
+        x = self.shared_mlp(x, p + 'feat.conv2', p + 'feat.bn2')
+        g = TF.max_points(self.shared_mlp(x, p + 'feat.conv3', p + 'feat.bn3', relu=False))
+        x = torch.cat([g.unsqueeze(2).expand(-1, -1, N), pointfeat], 1)
+        for i in (1, 2, 3):
+            x = self.shared_mlp(x, f'{p}conv{i}', f'{p}bn{i}')
+        return TF.log_softmax_points(TF.linear_cols(x, self.P(p + 'conv4.weight'), self.P(p + 'conv4.bias')))
+
+    def flush_counters(self):
+        """num_batches_tracked += 1 for every BatchNorm layer evaluated since the last flush (callers that evaluate a branch on its own — the tests — call this themselves)."""
+        if self._nbt:
+            with torch.no_grad():
+                torch._foreach_add_(self._nbt, 1)
+            self._nbt = []
+
+
+class TrainGraph(Layers):
+    """`Layers` over the whole model, plus its wiring: backbones, necks, decoders, radar branch, fusion, head, PointNet++."""
+
+    def __init__(self, model):
+        if model.backbone not in ('en', 'mv', 'rv'):
+            raise NotImplementedError(f"training mode is not built for backbone={model.backbone!r} (inference only; 'en', 'mv' and 'rv' train)")
+        super().__init__(model)
+        self.m = model
+        self.cfg = EDGENEXT[model.phi]
+        self.w = WIDTHS[model.phi]
 
     def upsample(self, x, pfx):
         """Upsample: BaseConv 1x1 + bilinear x2, align_corners (neck/ghostdualfpn.py:28-39)."""
@@ -254,7 +315,7 @@ class TrainGraph:
 
     def mobilevit(self, x, pfx):
         """MobileViT.forward (mobilevit.py:198-222)."""
-        ch = MOBILEVIT[self.m.phi]
+        ch = MOBILEVIT[self.m.phi]['ch']
         x = self.conv_bn_silu(x, pfx + '.conv1', 2, 1)
         x = self.mv2block(x, pfx + '.mv2.0', 1, ch[1])
         x = self.mv2block(x, pfx + '.mv2.1', 2, ch[2])
@@ -393,49 +454,7 @@ class TrainGraph:
             outs.append(torch.cat([self.conv(r, f'det_head.reg_preds.{k}'), self.conv(r, f'det_head.obj_preds.{k}'), self.conv(c, f'det_head.cls_preds.{k}')], 1))
         return outs
 
-    # ---------------------------------------------------------------------------------------------- PointNet
-    def shared_mlp(self, x, conv, bn, relu=True):
-        """Conv1d(k=1) / Linear + BatchNorm1d [+ ReLU] on [B, C, N] (pointnet_utils.py:29-31, 69-71, 124-127)."""
-        self._nbt.append(self.b[bn + '.num_batches_tracked'])
-        return _SharedMLP1dFn.apply(x, self.P(conv + '.weight'), self.P(conv + '.bias'), self.P(bn + '.weight'), self.P(bn + '.bias'),
-                                    self.b[bn + '.running_mean'], self.b[bn + '.running_var'], True, BN_MOMENTUM, 1e-5, relu)
-
-    def fc_bn(self, x, fc, bn):
-        """Linear + BatchNorm1d + ReLU on [B, C]: the batch is the axis of the statistics, i.e. the shared MLP on [1, C, B]."""
-        return self.shared_mlp(x.t().contiguous().unsqueeze(0), fc, bn).squeeze(0).t()
-
-    def stn(self, x, pfx, k):
-        """STN3d / STNkd (pointnet_utils.py:10-85)."""
-        y = self.shared_mlp(x, pfx + '.conv1', pfx + '.bn1')
-        y = self.shared_mlp(y, pfx + '.conv2', pfx + '.bn2')
-        y = _MaxPointsFn.apply(self.shared_mlp(y, pfx + '.conv3', pfx + '.bn3'))
-        y = self.fc_bn(self.fc_bn(y, pfx + '.fc1', pfx + '.bn4'), pfx + '.fc2', pfx + '.bn5')
-        y = _LinearFn.apply(y.t().contiguous().unsqueeze(0), self.P(pfx + '.fc3.weight'), self.P(pfx + '.fc3.bias')).squeeze(0).t()
-        return (y + torch.eye(k, dtype=y.dtype, device=y.device).reshape(1, k * k)).view(-1, k, k)
-
-    def pointnet(self, pts):
-        """PointNet_SEG.forward / PointNetEncoder.forward (pointnet_sem_seg.py:26-37, pointnet_utils.py:103-133)."""
-        p = 'pc_seg_model'
-        B, D, N = pts.shape
-        trans = self.stn(pts, p + '.feat.stn', 3)
-        xyz = _BmmPointsFn.apply(pts[:, :3].contiguous(), trans)
-        x = torch.cat([xyz, pts[:, 3:]], 1) if D > 3 else xyz
-        x = self.shared_mlp(x, p + '.feat.conv1', p + '.feat.bn1')
-        x = _BmmPointsFn.apply(x, self.stn(x, p + '.feat.fstn', 32))
-        pointfeat = x
-        x = self.shared_mlp(x, p + '.feat.conv2', p + '.feat.bn2')
-        g = _MaxPointsFn.apply(self.shared_mlp(x, p + '.feat.conv3', p + '.feat.bn3', relu=False))
-        x = torch.cat([g.unsqueeze(2).expand(-1, -1, N), pointfeat], 1)
-        for i in (1, 2, 3):
-            x = self.shared_mlp(x, f'{p}.conv{i}', f'{p}.bn{i}')
-        return _LogSoftmaxPointsFn.apply(_LinearFn.apply(x, self.P(p + '.conv4.weight'), self.P(p + '.conv4.bias')))
-
     # ---------------------------------------------------------------------------------------------- PointNet++ (OUR OWN specification, DESIGN 5b / spec.py::PN2)
-    def rows_mlp(self, rows, conv, bn):
-        """Conv (k = 1) + BatchNorm + ReLU over ROWS [R, C]: the statistics run over all rows — BatchNorm2d over (B, centroids, samples) of a set-abstraction level,
-        BatchNorm1d over (B, points) of a propagation level — i.e. the shared MLP on [1, C, R]."""
-        return self.shared_mlp(rows.t().contiguous().unsqueeze(0), conv, bn).squeeze(0).t().contiguous()
-
     def pointnet2(self, pts):
         """Set abstraction x 4 (farthest-point sampling, ball query, shared MLP, max over the ball), feature propagation x 4 (3-NN interpolation + skip + shared MLP), head.
         The reference snapshot has no PointNet++ code (nets/Achelous.py:31-32): structure, widths, radii and tie rules are spec.py::PN2's, the same ones the inference
@@ -461,7 +480,7 @@ class TrainGraph:
                     names = (f'{p}.sa{k + 1}.conv_blocks.{j}.{i}', f'{p}.sa{k + 1}.bn_blocks.{j}.{i}') if 'scales' in cfg else (f'{p}.sa{k + 1}.mlp_convs.{i}', f'{p}.sa{k + 1}.mlp_bns.{i}')
                     x = self.shared_mlp(x, *names)
                 cout = x.shape[1]
-                f = _MaxPointsFn.apply(x.view(cout, B * S, K))                   # max over the ball: [cout, B*S]
+                f = TF.max_points(x.view(cout, B * S, K))                   # max over the ball: [cout, B*S]
                 outs.append(f.t().contiguous().view(B, S, cout))
             levels.append((new_xyz, outs[0] if len(outs) == 1 else torch.cat(outs, 2).contiguous()))
         cur = levels[-1][1]
@@ -474,8 +493,8 @@ class TrainGraph:
                 h = self.rows_mlp(h, f'{p}.fp{lvl + 1}.mlp_convs.{i}', f'{p}.fp{lvl + 1}.mlp_bns.{i}')
             cur = h.view(B, xyz1.shape[1], widths[-1])
         h = self.rows_mlp(cur.reshape(B * N, -1), p + '.conv1', p + '.bn1')
-        z = _LinearFn.apply(h.view(B, N, -1).transpose(1, 2).contiguous(), self.P(p + '.conv2.weight'), self.P(p + '.conv2.bias'))       # [B, classes, N]
-        return _LogSoftmaxPointsFn.apply(z)
+        z = TF.linear_cols(h.view(B, N, -1).transpose(1, 2).contiguous(), self.P(p + '.conv2.weight'), self.P(p + '.conv2.bias'))       # [B, classes, N]
+        return TF.log_softmax_points(z)
 
     # ---------------------------------------------------------------------------------------------- Achelous.forward (nets/Achelous.py:49-53)
     def forward(self, x, x_radar, x_pc):
@@ -491,12 +510,6 @@ class TrainGraph:
         self.flush_counters()
         return det, se, lane, pc
 
-    def flush_counters(self):
-        """num_batches_tracked += 1 for every BatchNorm layer evaluated since the last flush (callers that evaluate a branch on its own — the tests — call this themselves)."""
-        if self._nbt:
-            with torch.no_grad():
-                torch._foreach_add_(self._nbt, 1)
-            self._nbt = []
 
 
 class GraphedTrainStep:

@@ -352,10 +352,6 @@ int ach_train_bn_relu_fwd(const float* z, const float* mean, const float* var, c
                           int32_t N, float eps, int32_t relu, void* stream);
 int ach_train_bn_relu_bwd(const float* z, const float* y, const float* dy, const float* mean, const float* var, const float* gamma, float* dgamma,
                           float* dbeta, float* dz, int32_t B, int32_t C, int32_t N, float eps, int32_t relu, void* stream);
-/*   ach_train_dw3x3        depthwise 3x3 / stride 1 / pad 1 on [B,C,H,W], w [C,9]; flip = 1 mirrors the taps (the input gradient)
- *   ach_train_dw3x3_wgrad  its weight gradient dw [C,9] = sum over (B,H,W) of dz x shifted x   (GhostModule cheap operation, ghost_conv.py:19-23) */
-int ach_train_dw3x3(const float* x, const float* w, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t flip, void* stream);
-int ach_train_dw3x3_wgrad(const float* x, const float* dz, float* dw, int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
 /*   ach_train_max_points   max over the N points of rows = B*C rows with the arg-max (dy == NULL: forward x -> y, idx; else backward dy, idx -> dx)
  *   ach_train_log_softmax  log-softmax over the classes of z [B,K,N] written as [B,N,K] (dy == NULL: forward; else y, dy -> dz [B,K,N])
  *                          (pointnet_utils.py:32,127; pointnet_sem_seg.py:34-37) */
@@ -374,6 +370,7 @@ int ach_resample_pass_u8(const uint8_t* src, uint8_t* dst, const int32_t* bounds
  *   ach_train_act            kind 0 ReLU, 1 SiLU, 2 GELU (erf), 3 sigmoid: out = f(x) | dy * f'(x)
  *   ach_train_layernorm      over C of elements (r, c, i) at (r*C + c)*inner + i (channels-last rows: inner 1; channels_first maps: inner H*W)
  *   ach_train_dwconv         depthwise k x k, stride 1, pad k/2, w [C,k*k]; flip = 1: the input gradient;  _wgrad: dw [C,k*k]
+ *                            (the ONE depthwise family: the Ghost blocks' 3x3, ghost_conv.py:19-23, 47-56, runs through it in the model and stand-alone)
  *   ach_train_im2col         col [B][C*kh*kw][Ho*Wo] <- x (backward = 1: dx <- dcol), dense convolutions run through ach_train_gemm
  *   ach_train_softmax        over the last dimension d of [rows, d]
  *   ach_train_upsample2x     bilinear x2, align_corners=True: [planes,h,w] -> [planes,2h,2w] (backward = 1: the adjoint)

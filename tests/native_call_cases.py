@@ -124,6 +124,10 @@ def _ghost_bottleneck():
     _back(train_ops.GhostBottleneck(3, 4, 5).train()(_r(2, 3, 6, 5, grad=True)))
 
 
+def _pointnet_seg():
+    _back(train_ops.PointNetSeg(8, 5).train()(_r(2, 5, 16, grad=True)))
+
+
 def _batchnorm():
     _back(TF.batchnorm(_r(2, 3, 6, 5, grad=True), _r(3, seed=1, grad=True), _r(3, seed=2, grad=True), torch.zeros(3), torch.ones(3), True, relu=True))
 
@@ -154,7 +158,7 @@ for _stride in (1, 2):
         for _g in (True, False):
             CASES[f'deform_s{_stride}_{_kname}_xgrad{int(_g)}'] = lambda s=_stride, k=_keep, g=_g: _deform(s, k, g)
 CASES.update({'ghost_module': _ghost_module, 'ghost_bottleneck': _ghost_bottleneck, 'batchnorm_relu': _batchnorm, 'dwconv5_bias': _dwconv, 'bmm_nt': _bmm_nt,
-              'bmm_nn': _bmm_nn, 'bmm_points': _bmm_points})
+              'bmm_nn': _bmm_nn, 'bmm_points': _bmm_points, 'pointnet_seg': _pointnet_seg})
 
 
 def record(fn):

@@ -70,7 +70,7 @@ def test_bindings_derived_from_the_header_have_the_declared_signatures():
     for name, (restype, argtypes) in literal.items():
         assert eng_mod.PROTOTYPES[name] == (restype, argtypes), name
     counts = _declared_parameter_counts()
-    assert list(eng_mod.NativeLibrary.SYMBOLS) == list(eng_mod.PROTOTYPES) and set(counts) == set(eng_mod.PROTOTYPES) and len(counts) == 90
+    assert list(eng_mod.NativeLibrary.SYMBOLS) == list(eng_mod.PROTOTYPES) and set(counts) == set(eng_mod.PROTOTYPES) and len(counts) == 88
     L = emu_library().lib
     for name, n in counts.items():
         fn = getattr(L, name)

@@ -321,10 +321,17 @@ REPLAY_REFERENCES = {
     'maxpool_same': lambda x, k: F.max_pool2d(x, k, 1, k // 2),
     'avgpool3': lambda x: F.avg_pool2d(x, 3, 1, 1),
     'deform_conv3x3': lambda x, offset, mask, weight, stride=1, pad=1: ref_deform_conv(x, offset, mask, weight, stride, pad),
+    'linear_cols': lambda x, weight, bias=None: F.conv1d(x, weight.reshape(weight.shape[0], x.shape[1], 1), bias),
+    'bmm_points': lambda x, T: T.transpose(1, 2) @ x,
+    'max_points': lambda x: x.max(2)[0],
+    'log_softmax_points': lambda z: F.log_softmax(z, 1).transpose(1, 2),
 }
 # reached by train_graph.py, not replayed: the PointNet++ geometry (integer indices out, coordinates in), which EN-GDF-PN does not run — each primitive is held against the
 # oracle directly, forward and adjoint, in tests/test_pn2_geometry.py (the whole branch in tests/test_pointnet2.py)
-REPLAY_NOT_COVERED = {'pn2_fps', 'pn2_group', 'pn2_interp'}
+# and the fused conv + BatchNorm node of the PointNet branch: at the STNs' fc layers its statistics run over the BATCH (2 samples in the emulated replay, 8 on the GPU), where a
+# float32 evaluation — torch's own as much as ours — is off by 1e-3 .. 5e-2 in max-norm (tests/test_train_ops.py::_run_pointnet), far above this replay's 2e-4 cap.  The node is held at
+# PointNet's layer widths with well-posed statistics in tests/test_train_ops.py (`_run` over SHAPES, emulated and on the GPU) and the branch end to end in `_run_pointnet`.
+REPLAY_NOT_COVERED = {'pn2_fps', 'pn2_group', 'pn2_interp', 'shared_mlp'}
 
 
 def _record_training_step(dev, batch):
@@ -336,7 +343,7 @@ def _record_training_step(dev, batch):
     # passes again.  It reads text, so a `TF.<name>` in a comment trips it too, and a name imported from train_functional directly would slip past it: keep the `TF.` form there.
     names = sorted(n for n in set(re.findall(r'\bTF\.([a-z]\w*)', inspect.getsource(train_graph))) if callable(getattr(TF, n)))
     assert set(names) == set(REPLAY_REFERENCES) | REPLAY_NOT_COVERED, sorted(set(names) ^ (set(REPLAY_REFERENCES) | REPLAY_NOT_COVERED))
-    calls, originals = {}, {n: getattr(TF, n) for n in names}
+    calls, originals = {}, {n: getattr(TF, n) for n in names if n in REPLAY_REFERENCES}
 
     def recorder(name, fn):
         sig = inspect.signature(fn)
@@ -353,12 +360,12 @@ def _record_training_step(dev, batch):
     m = m.to(dev).train()
     x, xr, xp = (t.to(dev) for t in make_inputs(batch, 13, resolution=320, num_points=512, pc_channels=5))
     try:
-        for n in names:
+        for n in originals:
             setattr(TF, n, recorder(n, originals[n]))
         det, se, lane, pc = m(x, xr, xp)
         sum((o ** 2).mean() for o in (*det, se, lane, pc)).backward()
     finally:
-        for n in names:
+        for n in originals:
             setattr(TF, n, originals[n])
     return list(calls)
 

@@ -176,7 +176,8 @@ def _run_module(dev, native, ref, xshape, seed=0):
 
 
 GHOST_CASES = [('module', (48, 48, True), (2, 48, 12, 10)), ('module', (32, 9, True), (2, 32, 9, 16)), ('module', (96, 48, False), (1, 96, 8, 8)),
-               ('bottleneck', (96, 96, 48), (2, 96, 10, 10)), ('bottleneck', (32, 32, 32), (2, 32, 6, 7))]
+               ('bottleneck', (96, 96, 48), (2, 96, 10, 10)), ('bottleneck', (32, 32, 32), (2, 32, 6, 7)), ('bottleneck', (32, 48, 24), (2, 32, 6, 7))]
+# (rows of 10 and 7 take the depthwise kernel with one output per thread, rows of 16 and 8 the one with four; (32, 32, 32) is the identity form, (32, 48, 24) has mid != in)
 
 
 def _ghost_pair(kind, args):
@@ -196,7 +197,7 @@ def test_emulated_ghost_blocks_forward_backward_match_autograd(kind, args, xshap
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('kind,args,xshape', GHOST_CASES + [('bottleneck', (192, 192, 96), (64, 192, 20, 20)), ('module', (32, 9, True), (8, 32, 320, 320))])
+@pytest.mark.parametrize('kind,args,xshape', GHOST_CASES[:5] + [('bottleneck', (192, 192, 96), (64, 192, 20, 20)), ('module', (32, 9, True), (8, 32, 320, 320))] + GHOST_CASES[5:])          # (later cases behind the two large ones: the ids of the earlier ones stay)
 def test_gpu_ghost_blocks_forward_backward_match_autograd(kind, args, xshape):
     print(_run_module('cuda', *_ghost_pair(kind, args), xshape))
 
@@ -328,6 +329,99 @@ def test_pointnet_seg_state_dict_is_the_reference_pc_seg_model():
     ref = [(k[len('pc_seg_model.'):], tuple(s)) for k, s, _ in meta['keys'] if k.startswith('pc_seg_model.')]
     mine = [(k, tuple(v.shape)) for k, v in train_ops.PointNetSeg(8, 5).state_dict().items()]
     assert len(ref) == 118 and ref == mine
+
+
+# ---------------------------------------------------------------------------------------- eval mode of the stand-alone blocks; the model's branch through the stand-alone module
+def _run_eval(dev, native, ref, xshape, seed=0):
+    """`.eval()` under no_grad — the running-statistics branch of the shared evaluator — against the torch statement in float64 `.eval()`, with conditioned running
+    statistics (not the 0 / 1 defaults).  Bound: tests/test_train_functional.py's rule max(FLOOR, F_YARD x yardstick), the yardstick being torch's float32 `.eval()` of the
+    same module against the same truth.  The BatchNorm counters stay where they are in eval mode and move by exactly 1 per training forward."""
+    import copy
+    import test_train_functional as P
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for k, v in ref.named_buffers():
+            if k.endswith('running_mean'):
+                v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+            if k.endswith('running_var'):
+                v.copy_(torch.rand(v.shape, generator=g) + 0.5)
+    native.load_state_dict(ref.state_dict(), strict=True)
+    truth, native, ref = copy.deepcopy(ref).double().eval(), native.to(dev).eval(), ref.eval()
+    x = torch.randn(*xshape, generator=g) * 0.5
+    counters = lambda: [int(v) for k, v in native.named_buffers() if k.endswith('num_batches_tracked')]
+    before = counters()
+    assert len(before) > 0
+    with torch.no_grad():
+        yt, yf, yn = truth(x.double()), ref(x), native(x.to(dev))
+    assert counters() == before
+    err, yard = P._rel(yn, yt), P._rel(yf, yt)
+    bound = max(P.FLOOR, P.F_YARD * yard)
+    print(f'eval {type(native).__name__}{tuple(xshape)} on {dev}: native {err:.3e}, torch float32 {yard:.3e}, bound {bound:.3e}')
+    assert err < bound, (err, yard, bound)
+    native.train()
+    for n in (1, 2):
+        native(x.to(dev))
+        assert counters() == [c + n for c in before]
+
+
+EVAL_CASES = {'bottleneck': (lambda: (train_ops.GhostBottleneck(32, 48, 24), _torch_bottleneck(32, 48, 24)), (2, 32, 6, 7)),
+              'pointnet': (lambda: (train_ops.PointNetSeg(8, 5), _TorchPointNetSeg(8, 5)), (2, 5, 16))}
+
+
+@pytest.mark.parametrize('name', list(EVAL_CASES))
+def test_emulated_blocks_in_eval_mode_use_the_running_statistics(name):
+    from emu_util import emu_library
+    train_ops._lib.test_library = emu_library()
+    try:
+        torch.manual_seed(0)
+        _run_eval('cpu', *EVAL_CASES[name][0](), EVAL_CASES[name][1])
+    finally:
+        train_ops._lib.test_library = None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', list(EVAL_CASES))
+def test_gpu_blocks_in_eval_mode_use_the_running_statistics(name):
+    torch.manual_seed(0)
+    _run_eval('cuda', *EVAL_CASES[name][0](), EVAL_CASES[name][1])
+
+
+def _model_step_through_pointnet_seg(dev):
+    """One whole-model training step (tests/test_train_graph.py::_step) and the stand-alone `PointNetSeg` carrying the model's `pc_seg_model.*` state dict, on the same
+    points and cotangent: bit-identical log-probabilities and parameter gradients — both are ONE statement of the branch (train_graph.Layers.pointnet)."""
+    import test_train_graph as G
+    from achelous_amd.synth import make_inputs
+    meta, _, m, outs, _ = G._step(dev)
+    pfx = 'pc_seg_model.'
+    alone = train_ops.PointNetSeg(meta['ctor']['pc_classes'], meta['ctor']['pc_channels'])
+    alone.load_state_dict({k[len(pfx):]: v for k, v in m.state_dict().items() if k.startswith(pfx)}, strict=True)
+    alone = alone.to(dev).train()
+    xp = make_inputs(meta['batch'], meta['input_seed'], resolution=meta['ctor']['resolution'], num_points=meta['num_points'], pc_channels=meta['ctor']['pc_channels'],
+                     radar_cells=meta['radar_cells'])[2]
+    g = torch.Generator().manual_seed(meta['cotangent_seed'])
+    cot = [torch.randn(o.shape, generator=g, dtype=torch.float64).float().to(dev) for o in outs][-1]
+    pc = alone(xp.to(dev))
+    (pc * cot).sum().backward()
+    assert torch.equal(pc, outs[-1])
+    theirs = {k[len(pfx):]: v for k, v in m.named_parameters() if k.startswith(pfx)}
+    mine = dict(alone.named_parameters())
+    assert list(mine) == list(theirs) and len(mine) == 70
+    for k, v in mine.items():
+        assert torch.equal(v.grad, theirs[k].grad), k
+
+
+def test_emulated_model_step_and_stand_alone_pointnet_are_one_code_path():
+    from emu_util import emu_library
+    train_ops._lib.test_library = emu_library()
+    try:
+        _model_step_through_pointnet_seg('cpu')
+    finally:
+        train_ops._lib.test_library = None
+
+
+@pytest.mark.gpu
+def test_gpu_model_step_and_stand_alone_pointnet_are_one_code_path():
+    _model_step_through_pointnet_seg('cuda')
 
 
 # ---------------------------------------------------------------------------------------- both sides of every shape-dependent dispatch of the C entries
