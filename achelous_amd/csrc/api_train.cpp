@@ -1,5 +1,6 @@
 // api_train.cpp — the stateless entries of the training-mode kernels (k_train.h, k_train2.h, k_train3.h), the training losses (k_loss.h) and the validation
 // metrics (k_metrics.h): argument checks and launch policy.  fp32, no handle; errors through ach_last_error(NULL).  See api.cpp / api_util.h.
+// Also the optimizer step and weight EMA over the flat training-state arena (k_optim.h; declared in include/achelous_optim.h).
 #include <algorithm>
 #include <atomic>
 #include <map>
@@ -11,6 +12,8 @@
 #include "k_train3.h"
 #include "k_loss.h"
 #include "k_metrics.h"
+#include "k_optim.h"
+#include "../../include/achelous_optim.h"
 
 // in an entry: `st` is its stream.  One thread per element of `total`, or `nblocks` workgroups, of 256 threads
 #define ACH_TRAIN_1D(kern, p, total) ACH_LAUNCH(kern, dim3(unsigned(ach::cdivl((total), 256))), dim3(256), st, p)
@@ -436,6 +439,31 @@ int ach_eval_match(const float* rows, const int32_t* counts, int32_t yx_order, i
         for (int t = 0; t < T; ++t) p.thr[t] = thresholds[t];
         p.flags = flags; p.match = match; p.iou = iou; p.score = score; p.gt_per_class = reinterpret_cast<unsigned long long*>(gt_per_class);
         ACH_TRAIN_ROWS(ach::match_kernel, p, B);
+    });
+}
+
+// ---- optimizer step and weight EMA (k_optim.h, include/achelous_optim.h): stateless, every buffer the caller's.  The kernels index by chunk number below `chunks` only.
+int ach_optim_tick(double* hyper, void* stream) {
+    return stateless(stream, [&](hipStream_t st) {
+        need(hyper && (reinterpret_cast<uintptr_t>(hyper) & 7u) == 0, "ach_optim_tick");
+        ACH_LAUNCH(ach::optim_tick_kernel, dim3(1), dim3(64), st, hyper);
+    });
+}
+// workgroups of the step: four chunks (4 KB of every arena) per workgroup and iteration, grid-stride above 2048 = eight resident workgroups on each of the 256 compute
+// units, enough 16-byte requests in flight to stream from HBM
+static int optim_blocks(long chunks) { return int(std::max<long>(1, std::min<long>(ach::cdivl(chunks, 4), 2048))); }
+int ach_optim_step(float* state, float* ema, const float* grad, float* m1, float* m2, const int32_t* flags, int32_t* t, const double* hyper, int64_t chunks,
+                   int64_t param_chunks, int32_t kind, int32_t nesterov, double momentum, double beta1, double beta2, double eps, void* stream) {
+    return stateless(stream, [&](hipStream_t st) {
+        need(state && grad && flags && hyper, "ach_optim_step: state, grad, flags and hyper");
+        need(chunks > 0 && param_chunks > 0 && param_chunks <= chunks && chunks <= (int64_t(1) << 30), "ach_optim_step: 0 < param_chunks <= chunks <= 2^30");
+        need(kind >= ach::OPT_SGD && kind <= ach::OPT_ADAMW, "ach_optim_step: kind 0 (sgd), 1 (adam) or 2 (adamw)");
+        need(kind == ach::OPT_SGD ? (momentum == 0.0 || m1 != nullptr) : (m1 && m2 && t), "ach_optim_step: m1 for momentum; m1, m2 and t for Adam");
+        need(kind == ach::OPT_SGD || (beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0), "ach_optim_step: betas in [0, 1), eps >= 0");
+        need(aligned16(state, ema, grad, m1, m2) && (reinterpret_cast<uintptr_t>(hyper) & 7u) == 0 && ((reinterpret_cast<uintptr_t>(flags) | reinterpret_cast<uintptr_t>(t)) & 3u) == 0,
+             "ach_optim_step: arenas 16-byte aligned");
+        ach::OptimStepParams p{state, ema, grad, m1, m2, flags, t, hyper, int(chunks), int(param_chunks), kind, nesterov != 0, float(momentum), beta1, beta2, eps};
+        ACH_LAUNCH(ach::optim_step_kernel, dim3(unsigned(optim_blocks(long(chunks)))), dim3(256), st, p);
     });
 }
 

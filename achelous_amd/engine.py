@@ -78,10 +78,14 @@ for _name in EXTENSION_HEADERS:
 with open(os.path.join(os.path.dirname(HEADER), 'achelous_points.h')) as _f:
     POINT_ENTRIES = parse_header(_f.read())
 
+# include/achelous_optim.h (the optimizer step and weight EMA over the flat training-state arena, achelous_amd/optim.py): likewise
+with open(os.path.join(os.path.dirname(HEADER), 'achelous_optim.h')) as _f:
+    OPTIM_ENTRIES = parse_header(_f.read())
+
 
 class NativeLibrary:
-    """dlopen + prototypes for every symbol declared in include/achelous.h (SYMBOLS), in its extension headers (EXTENSIONS) and in include/achelous_points.h
-    (POINT_ENTRIES), derived from the headers themselves (parse_header)."""
+    """dlopen + prototypes for every symbol declared in include/achelous.h (SYMBOLS), in its extension headers (EXTENSIONS), in include/achelous_points.h
+    (POINT_ENTRIES) and in include/achelous_optim.h (OPTIM_ENTRIES), derived from the headers themselves (parse_header)."""
     SYMBOLS = tuple(PROTOTYPES)
 
     def __init__(self, path):
@@ -92,7 +96,7 @@ class NativeLibrary:
         self.lib = ctypes.CDLL(path)
         # (an entry is bound where the library exports it: the co-residency tests also load libraries built from older sources; tests/test_abi_and_host.py
         #  holds the product to every declared symbol, and calling an entry a library lacks raises AttributeError)
-        for name, (restype, argtypes) in {**PROTOTYPES, **EXTENSIONS, **POINT_ENTRIES}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **EXTENSIONS, **POINT_ENTRIES, **OPTIM_ENTRIES}.items():
             fn = getattr(self.lib, name, None)
             if fn is not None:
                 fn.restype, fn.argtypes = restype, argtypes

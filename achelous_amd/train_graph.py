@@ -10,7 +10,7 @@ kernels.  What torch does here is tensor plumbing: views, `cat` / `split` / chan
 gradients autograd routes.  fp32 on GPU tensors only; there is no PyTorch-op or CPU fallback.
 
 Built for the EdgeNeXt ('en'), MobileViT ('mv') and RepViT ('rv') backbones (PoolFormer is inference only), Ghost-Dual-FPN ('gdf') and CSP-Dual-FPN
-('cdf') necks, PointNet ('pn'), nano head.  PointNet++ (our own specification, no reference) raises NotImplementedError in training mode.
+('cdf') necks, PointNet ('pn') and PointNet++ ('pn2', 'pn2_msg': our own specification, no reference; `TrainGraph.pointnet2`), nano head.
 """
 import math
 
@@ -524,7 +524,9 @@ class GraphedTrainStep:
 
     Requirements (those of any whole-step capture): fixed shapes and dtypes (the example tensors'), a `loss_fn(outputs, *targets) -> scalar tensor` made of torch ops without host
     synchronisation (no `.item()`, no data-dependent Python control flow), an optimizer whose step is capture-safe (SGD; Adam / AdamW with `capturable=True`), and no change of
-    `requires_grad` flags or parameter identity afterwards.  `outputs` = `(det_list, se, lane, pc)` as `forward` returns them; `step.outputs` holds the last replay's.
+    `requires_grad` flags or parameter identity afterwards.  Hyperparameters that are Python scalars of a torch optimizer (the learning rate) are baked into the capture;
+    an optimizer with `sync_hyperparameters()` / `mark_updated()` / `graph_state()` (optim.FusedOptimizer) keeps them in device memory instead: its learning rate is read
+    on every replay, and its momentum, EMA and counters are restored after the warm-up like the model's own state.  `outputs` = `(det_list, se, lane, pc)` as `forward` returns them; `step.outputs` holds the last replay's.
     The warm-up steps that precede the capture run on the example batch and are UNDONE: parameters, BatchNorm statistics and optimizer state are restored in place.
     If the model has already run EAGER training steps, drop every reference to their outputs / losses first: a live autograd graph keeps the parameters' AccumulateGrad nodes
     bound to the eager steps' stream, and replaying them inside a capture is not legal (measured: hipStreamEndCapture crashes)."""
@@ -543,6 +545,9 @@ class GraphedTrainStep:
         saved_model = {k: v.detach().clone() for k, v in model.state_dict().items()}
         had_state = len(optimizer.state) > 0
         saved_opt = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()} for p, st in optimizer.state.items()} if had_state else None
+        # an optimizer that keeps its state outside `optimizer.state` (optim.FusedOptimizer: flat arenas, the EMA and its counters) names the tensors a step writes
+        graph_state = optimizer.graph_state() if hasattr(optimizer, 'graph_state') else []
+        saved_graph_state = [t.detach().clone() for t in graph_state]
 
         def run():
             outs = model(*self.inputs)
@@ -575,6 +580,10 @@ class GraphedTrainStep:
                             v.copy_(saved_opt[id(p)][k])
                         else:
                             v.zero_()
+            for t, saved in zip(graph_state, saved_graph_state):
+                t.copy_(saved)
+        if hasattr(optimizer, 'mark_updated'):
+            optimizer.mark_updated()
         self.steps = 0
 
     @torch.no_grad()
@@ -590,6 +599,10 @@ class GraphedTrainStep:
 
     def __call__(self, x, x_radar, x_points, *targets):
         self._load((x, x_radar, x_points), targets)
+        if hasattr(self.optimizer, 'sync_hyperparameters'):
+            self.optimizer.sync_hyperparameters()                 # a learning rate set since the last replay: into the device array the captured step reads
         self.graph.replay()
+        if hasattr(self.optimizer, 'mark_updated'):
+            self.optimizer.mark_updated()                         # the replay wrote parameters through raw pointers: eval() must re-fold
         self.steps += 1
         return self.loss.detach()
