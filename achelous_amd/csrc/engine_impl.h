@@ -41,6 +41,7 @@ namespace ach {
     } while (0)
 
 static inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
+constexpr int ACH_MAX_RESOLUTION = 864;      // largest input a plan is built for: see build()
 
 // ================================================================================================ Engine<T>
 template <class T>
@@ -2395,6 +2396,9 @@ public:
     // ------------------------------------------------------------------------------------------ plan (a1)
     void build() {
         if (cfg.resolution % 32 || cfg.resolution < 64) throw AchError{ACH_ERR_INVALID, "resolution must be a multiple of 32"};
+        // the forward is verified against the oracle, tap by tap, up to 864 x 864 (tests/test_engine_envelope.py): the last size whose stride-32 map (27 x 27) fits
+        // the SPP pooling tile, and 54 segments per radar row.  Nothing above it has been looked at.
+        if (cfg.resolution > ACH_MAX_RESOLUTION) throw AchError{ACH_ERR_UNSUPPORTED, "resolution above the verified envelope (at most " + std::to_string(ACH_MAX_RESOLUTION) + ")"};
         // enqueue order = plan order: the two side branches first, so they are already running while the (longest) image
         // path is being enqueued on the caller's stream
         A r[3];

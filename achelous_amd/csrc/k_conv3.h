@@ -261,8 +261,8 @@ __global__ __launch_bounds__(256, KS == 3 ? 4 : ACH_RCF_WIDE_WAVES) void rc_fron
             else xf[s] = *reinterpret_cast<const uint4*>(xp + off[s]);
         }
     };
-    unsigned active = 0xffffffffu;                                  // bit t: segment t of this row needs the full path
-    if (p.occ) {                                                    // ntiles <= 32 (engine)
+    unsigned active = 0xffffffffu;                                  // bit t: segment t of this row's FIRST span of 32 needs the full path (further spans: every segment does, see take())
+    if (p.occ) {                                                    // masks exist only for rows of <= 32 segments (engine: x.W / 16 <= 32); the ballots below keep 32 bits
         unsigned cols = 0;                                          // lane t: columns of segment t occupied in rows oy - occ_r .. oy + occ_r
         if (lane < ntiles) {                                        // fixed trip count (rows clamped into the map: duplicates do not change an OR)
             const unsigned short* f = p.occ + long(b) * p.H * ntiles + lane;
@@ -369,23 +369,32 @@ __global__ __launch_bounds__(256, KS == 3 ? 4 : ACH_RCF_WIDE_WAVES) void rc_fron
     }
     // Segments are dealt to the four waves by RANK among the active (and among the empty) ones, not by position: occupied cells come
     // in clusters, and position-strided waves would leave one wave with a row's whole cluster.
+    // A row is walked in SPANS of 32 segments: `rem` holds the segments left in the span that starts at segment `span`, `span_end` is where the
+    // walk stops.  Rows of up to 512 pixels are one span (the only case with occupancy masks: `active`, `tmask` and the compact tiles describe
+    // the first span); wider rows have no masks (p.occ is null past 32 segments) and every further span is taken whole.
     const unsigned tmask = ntiles >= 32 ? 0xffffffffu : ((1u << ntiles) - 1u);
     unsigned rem = active & tmask;
+    int span = 0, span_end = ntiles;
     if (compact) {
         if constexpr (NARROW) {
-        const int ctiles = (ntot + 15) / 16;                       // <= 32 (Wd <= 512)
+        const int ctiles = (ntot + 15) / 16;                       // <= 32: compact needs Wd <= 512 (above), so ntot <= 512
         rem = ctiles >= 32 ? 0xffffffffu : ((1u << ctiles) - 1u);
+        span_end = ctiles;
         plist_w = &plist[wave][0]; plist_n = ntot;
         }
     }
     int rank = 0;
-    auto take = [&]() -> int {                                      // this wave's next segment of `rem` (consumed), or -1
-        while (rem) {
-            const int t = __ffsll(static_cast<long long>(rem)) - 1;
-            rem &= rem - 1u;
-            if (p.rows4 || (rank++ & 3) == wv) return t;
+    auto take = [&]() -> int {                                      // this wave's next segment of the row (consumed), or -1
+        for (;;) {
+            while (rem) {
+                const int t = __ffsll(static_cast<long long>(rem)) - 1;
+                rem &= rem - 1u;
+                if (p.rows4 || (rank++ & 3) == wv) return span + t;
+            }
+            span += 32;
+            if (span >= span_end) return -1;
+            rem = span_end - span >= 32 ? 0xffffffffu : ((1u << (span_end - span)) - 1u);
         }
-        return -1;
     };
     int tile = take();
     if (tile >= 0) fetch(tile);
