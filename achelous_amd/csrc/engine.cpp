@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "k_detect.h"
+#include "k_nmswide.h"
 #include "k_prepost.h"
 
 namespace ach {
@@ -316,12 +317,20 @@ int EngineBase::num_anchors() const {
     const int r = cfg.resolution;
     return (r / 8) * (r / 8) + (r / 16) * (r / 16) + (r / 32) * (r / 32);
 }
-size_t EngineBase::nms_workspace_bytes(int B) const { return size_t(B) * num_anchors() * (8 * sizeof(float) + sizeof(int) + 4 * sizeof(float)) + 512; }
+// the workspace of nms(): up to NMS_MAXA anchors nms_kernel's three regions (records, indices, sorted boxes); above it the wide path's (k_nmswide.h):
+// records and anchors by slot (whole tiles of 1024), the tiles' counts and maxima, sorted boxes and class ids.  One 256-byte round-up per region.
+size_t EngineBase::nms_workspace_bytes(int B) const {
+    const size_t A = size_t(num_anchors());
+    if (A <= size_t(NMS_MAXA)) return size_t(B) * A * (8 * sizeof(float) + sizeof(int) + 4 * sizeof(float)) + 512;
+    const size_t slots = size_t(cdivl(long(A), NMSW_TILE)) * NMSW_TILE;
+    return size_t(B) * (slots * (8 * sizeof(float) + sizeof(int)) + 16 * (sizeof(int) + sizeof(float)) + A * (4 * sizeof(float) + sizeof(int))) + 6 * 256;
+}
 
 void EngineBase::nms(int B, const float* decoded, float conf, float iou, int max_det, float* rows, int* idx, int* count,
                      void* workspace, hipStream_t s) {
     const int A = num_anchors();
-    if (A > NMS_MAXA) throw AchError{ACH_ERR_UNSUPPORTED, "device NMS supports up to 4096 anchors per image (resolution <= 416)"};
+    if (A > NMSW_MAXA) throw AchError{ACH_ERR_UNSUPPORTED, "device NMS supports up to 15309 anchors per image (resolution <= 864)"};
+    if (A > NMS_MAXA) { nms_wide(B, decoded, conf, iou, max_det, rows, idx, count, workspace, s); return; }
     NmsParams p;
     p.dec = decoded;
     p.scratch = static_cast<float*>(workspace);
@@ -330,6 +339,28 @@ void EngineBase::nms(int B, const float* decoded, float conf, float iou, int max
     p.rows = rows; p.kept = idx; p.count = count;
     p.B = B; p.A = A; p.NC5 = 5 + cfg.num_det; p.num_classes = cfg.num_det; p.max_det = max_det; p.conf = conf; p.iou = iou;
     ACH_LAUNCH(nms_kernel, dim3(unsigned(B)), dim3(NMS_THREADS), s, p);
+}
+
+// NMS_MAXA < A <= NMSW_MAXA: filter + compaction per tile of 1024 anchors, then one workgroup per image (k_nmswide.h)
+void EngineBase::nms_wide(int B, const float* decoded, float conf, float iou, int max_det, float* rows, int* idx, int* count,
+                          void* workspace, hipStream_t s) {
+    const int A = num_anchors();
+    const int tiles = int(cdivl(long(A), NMSW_TILE));
+    const long slots = long(B) * tiles * NMSW_TILE;
+    char* w = static_cast<char*>(workspace);
+    auto take = [&](long bytes) { char* at = w; w += round_up(bytes, 256); return at; };
+    NmsWideParams p;
+    p.dec = decoded;
+    p.rec = reinterpret_cast<float*>(take(slots * 8 * long(sizeof(float))));
+    p.rec_anchor = reinterpret_cast<int*>(take(slots * long(sizeof(int))));
+    p.tile_cnt = reinterpret_cast<int*>(take(long(B) * 16 * long(sizeof(int))));
+    p.tile_max = reinterpret_cast<float*>(take(long(B) * 16 * long(sizeof(float))));
+    p.sbox = reinterpret_cast<float*>(take(long(B) * A * 4 * long(sizeof(float))));
+    p.scls = reinterpret_cast<int*>(take(long(B) * A * long(sizeof(int))));
+    p.rows = rows; p.kept = idx; p.count = count;
+    p.B = B; p.A = A; p.NC5 = 5 + cfg.num_det; p.num_classes = cfg.num_det; p.max_det = max_det; p.tiles = tiles; p.conf = conf; p.iou = iou;
+    ACH_LAUNCH(nms_wide_filter_kernel, dim3(unsigned(tiles), unsigned(B)), dim3(NMSW_TILE), s, p);
+    ACH_LAUNCH(nms_wide_kernel, dim3(unsigned(B)), dim3(NMSW_TILE), s, p);
 }
 
 void EngineBase::correct_boxes(int B, int max_det, const float* rows, const int* count, int img_h, int img_w, int letterbox, float* out, hipStream_t s) {

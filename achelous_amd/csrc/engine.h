@@ -107,6 +107,8 @@ public:
     void note_region(const void* p, size_t bytes) { if (!measuring) t_regions.emplace_back(p, bytes); }
     void nms(int B, const float* decoded, float conf, float iou, int max_det, float* rows, int* idx, int* count,
              void* workspace, hipStream_t s);
+    void nms_wide(int B, const float* decoded, float conf, float iou, int max_det, float* rows, int* idx, int* count,
+                  void* workspace, hipStream_t s);            // more than NMS_MAXA anchors (k_nmswide.h); nms() dispatches
     size_t nms_workspace_bytes(int B) const;
     int num_anchors() const;
     void read_tap(const std::string& name, float* out, size_t cap);

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as _eng
+from .postprocess import NMS_MAX_ANCHORS
 from .spec import state_dict_spec
 
 
@@ -479,8 +480,8 @@ class Achelous(nn.Module):
                 return outputs()
             conf, iou, max_det = detect
             A = sum((R // s) ** 2 for s in (8, 16, 32))
-            if A > 4096:
-                raise NotImplementedError(f"device NMS handles up to 4096 anchors (resolution <= 416), got {A}")
+            if A > NMS_MAX_ANCHORS:
+                raise NotImplementedError(f"device NMS handles up to {NMS_MAX_ANCHORS} anchors (resolution <= 864), got {A}")
             max_det = int(max_det or A)
             decoded = torch.empty(B, A, nc5, dtype=torch.float32, device=dev)
             # one flat int32 buffer in the all-gather record layout of achelous_amd/dist.py; rows / idx / cnt are views of it (the

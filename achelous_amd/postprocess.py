@@ -11,6 +11,8 @@ import torch
 
 from ._native import stateless_handle as _handle          # _handle(num_det, resolution, dtype): the HIP library's handle on the current device
 
+NMS_MAX_ANCHORS = 15309         # 864 x 864 (csrc/k_nmswide.h NMSW_MAXA); up to 4096 anchors one launch (k_detect.h), above it two
+
 
 def decode_outputs(outputs, input_shape, local_rank=None):
     """[B,5+C,h,w] x 3 raw head maps -> [B, A, 5+C] fp32 (cx, cy, w, h normalised; sigmoid obj / cls)."""
@@ -43,8 +45,8 @@ def nms_device(prediction, num_classes, conf_thres, nms_thres, max_det=None):
     with torch.cuda.device(p.device):
         # A = (R/8)^2 + (R/16)^2 + (R/32)^2 = 21 (R/32)^2 for the square inputs the reference uses
         g = int(round((A / 21.0) ** 0.5))
-        if 21 * g * g != A or A > 4096:
-            raise NotImplementedError(f"device NMS handles square inputs up to 416x416 (3549 anchors), got {A} anchors")
+        if 21 * g * g != A or A > NMS_MAX_ANCHORS:
+            raise NotImplementedError(f"device NMS handles square inputs up to 864x864 ({NMS_MAX_ANCHORS} anchors), got {A} anchors")
         R = 32 * g
         h = _handle(num_classes, R, torch.float32)
         rows = torch.empty(B, max_det, 7, dtype=torch.float32, device=p.device)     # the kernel fills every slot (unused: 0 / -1)
